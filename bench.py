@@ -21,7 +21,18 @@ are reported beside as `cold_host_wall_ms_per_step`).  The warm number (K
 back-to-back steps between one barrier pair, host wall clock) is reported
 beside it under `warm`.
 
-  python bench.py [--gpus N --steps K --warmup W] [--algo auto|xsort|panel|rowsplit|csr5]
+A plain run sets up, warms up, times the K steps and prints the headline
+line (`ms_per_step` = one timed step).  `--full` adds everything else a line
+can carry, each in runs of its own after the timed steps: the other cache
+mode and the cold steps' host wall clock, the oracle check of a fresh step,
+the row-split and deterministic figures, the BASELINE configs[2]-[4] and
+SuiteSparse-class legs with their checks, the measured HBM ceiling and the
+CPU baselines.  `--dump-outputs DIR` writes the y the last timed step left
+(the workload is seeded: the same arguments give the same inputs) to
+DIR/y.npy.
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                  [--algo auto|xsort|panel|rowsplit|csr5]
                   [--cache cold|warm] [--partition cyclic|nnz]
 
 Default kernel (`auto`): the library's choice per rank slice (sblas_csr_pick):
@@ -1028,6 +1039,22 @@ def _gather_rows(torch, dist, dev, row, world):
     return np.stack([p.cpu().numpy() for p in parts])
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, y):
+    """`--dump-outputs DIR`: DIR/y.npy (float64) = the assembled y the timed
+    path's last step left, as its caller receives it.  A y above 64 MB is
+    cut to a fixed sample of its entries (seed 0, ascending indices), so two
+    builds given the same arguments write comparable files."""
+    y = np.ascontiguousarray(y, np.float64)
+    cap = DUMP_MAX_BYTES // 8
+    if y.size > cap:
+        y = y[np.sort(np.random.default_rng(0).choice(y.size, cap, replace=False))]
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "y.npy"), y)
+
+
 def _oracle_check(rowptr, col, val, x_h, y0, ys):
     """Post-timing verification (oracle = checker only): ys[0] within the
     per-row fp64 bound of the sequential row sum, every other y bit-identical."""
@@ -1224,12 +1251,19 @@ def run_ctx(args) -> int:
         sync_all()
         return time.perf_counter() - t, last
 
+    # the timed mode first; the other mode (reported beside) only with --full
+    warm_el = st = None
     if args.cache == "cold":
         st = cold()
-        warm_el, warm_last = warm()
     else:
         warm_el, warm_last = warm()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.get_y(0))
+    if args.cache == "warm":
+        # per-device kernel times come from cold steps, also for a warm headline
         st = cold()
+    elif args.full:
+        warm_el, warm_last = warm()
     # st[:, 0..2] = max over devices of kernel / exchange / step (ms); then
     # per device d: st[:, 3+3d .. 5+3d]
     step_ms = float(np.mean(st[:, 2]))
@@ -1315,14 +1349,13 @@ def run_ctx(args) -> int:
                    else "warm: host wall clock over K back-to-back steps"),
         "cache": args.cache,
         "scrub": f"{args.scrub} {args.scrub_gib} GiB",
-        ("warm" if args.cache == "cold" else "cold"): (
-            {"value": round(total_flops / (warm_el / args.steps) / 1e9, 3),
-             "ms_per_step": round(warm_el / args.steps * 1e3, 5),
-             "last_step_kernel_ms_max": round(float(warm_last[0]), 5)}
-            if args.cache == "cold" else
-            {"value": round(total_flops / (step_ms * 1e-3) / 1e9, 3), "ms_per_step": round(step_ms, 5)}),
     }
+    if args.cache == "cold" and warm_el is not None:
+        out["warm"] = {"value": round(total_flops / (warm_el / args.steps) / 1e9, 3),
+                       "ms_per_step": round(warm_el / args.steps * 1e3, 5),
+                       "last_step_kernel_ms_max": round(float(warm_last[0]), 5)}
     if args.cache == "warm":
+        out["cold"] = {"value": round(total_flops / (step_ms * 1e-3) / 1e9, 3), "ms_per_step": round(step_ms, 5)}
         out["value"] = round(total_flops / (warm_el / args.steps) / 1e9, 3)
         out["ms_per_step"] = round(warm_el / args.steps * 1e3, 5)
     if check is not None:
@@ -1356,6 +1389,15 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure and check everything else the line can carry: the "
+                         "other cache mode, the cold steps' host wall clock, the post-timing oracle check, "
+                         "the row-split and deterministic figures, the configs[2]-[4] and SuiteSparse-class "
+                         "legs, the measured HBM ceiling and the CPU baselines (each with its --no-* "
+                         "switch).  Without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the y their last step left to DIR/y.npy (float64; "
+                         "a fixed seeded sample above 64 MB)")
     ap.add_argument("--algo", choices=["auto", "rowsplit", "csr5", "panel", "xsort"], default="auto",
                     help="auto (default): the library's per-slice choice (sblas_csr_pick): rowsplit "
                          "for coalescing columns, else xsort from 2M nonzeros, else panel")
@@ -1367,7 +1409,7 @@ def main() -> int:
                     help="synth (default): BASELINE configs[1]'s scaled generator; stencil7 / "
                          "stencil27: 3-D finite-difference / FEM-block pattern on a --grid^3 mesh; "
                          "rmat: power-law graph with 2^--scale vertices (SuiteSparse-class checks "
-                         "of the north star's >= 60% target; not the headline)")
+                         "of the north star's >= 60%% target; not the headline)")
     ap.add_argument("--grid", type=int, default=160, help="stencil mesh edge (n = grid^3)")
     ap.add_argument("--scale", type=int, default=21, help="R-MAT scale (n = 2^scale)")
     ap.add_argument("--exchange", choices=["allgather", "allreduce"], default="allgather")
@@ -1375,16 +1417,16 @@ def main() -> int:
                     help="nccl (= RCCL over xGMI) for real runs; gloo only to rehearse the "
                          "multi-rank path with several ranks on one GPU")
     ap.add_argument("--check", action="store_true",
-                    help="(default; kept for old command lines) after timing, verify the assembled y "
-                         "of one fresh step against the oracle on rank 0 -> `check_vs_oracle`")
+                    help="(default under --full; kept for old command lines) after timing, verify the assembled "
+                         "y of one fresh step against the oracle on rank 0 -> `check_vs_oracle`")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the post-timing oracle check of the headline y (on by default)")
+                    help="skip the post-timing oracle check of the headline y (on by default under --full)")
     ap.add_argument("--cache", choices=["cold", "warm"], default="cold",
                     help="cold (default; SURVEY M1-cache / BASELINE.md: the headline uses cold "
                          "timing): a 1 GiB sweep (--scrub) before every timed step evicts the 256 MB "
                          "Infinity Cache and the L2s, each of the K steps bracketed by its own "
                          "barrier + synchronize; warm: K back-to-back steps bracketed by one "
-                         "barrier + synchronize on each side.  The other mode is always measured "
+                         "barrier + synchronize on each side.  With --full the other mode is measured "
                          "too and reported under `warm`/`cold`.")
     ap.add_argument("--partition", choices=["cyclic", "nnz"], default="cyclic",
                     help="N > 1 row distribution: cyclic equal-row chunks (default; no padding, "
@@ -1434,6 +1476,10 @@ def main() -> int:
     args = ap.parse_args()
     args.check_legs = not args.no_check_legs
     args.check = not args.no_check
+    if not args.full:  # a plain run measures the headline only
+        args.check = args.check_legs = False
+        args.no_rowsplit_beside = args.no_config3 = args.no_config4 = args.no_config5 = True
+        args.no_structured = args.no_peak = args.no_cpu_baseline = True
     if args.cpu_baseline_only:  # child of cpu_baseline(): host only, no torch, no GPU
         return cpu_baseline_child(args)
 
@@ -1565,7 +1611,7 @@ def main() -> int:
         # and the kernel arrive ~10 us later: rocprofv3's kernel trace of the
         # same command reads ~12 us less than unpadded events did).
         # The host wall clock around each cold step is measured in a second,
-        # spin-free pass and kept beside (wall_el).
+        # spin-free pass (run_cold_wall, --full) and kept beside (wall_el).
         # At N = 1 the step is the SpMV call alone (no exchange): its device
         # span is read from events the runtime stamps at the call's first
         # kernel start and last kernel end (sblas_spmv_timed), which excludes
@@ -1583,18 +1629,13 @@ def main() -> int:
                 step(evs[k])
             sync_barrier()
         if span_ms:
-            run_cold.wall_el = 0.0
             run_cold.xch = 0.0
-            wall_el = 0.0
-            for k in range(args.steps):
-                evict()
-                sync_barrier()
-                t0 = time.perf_counter()
-                step()
-                sync_barrier()
-                wall_el += time.perf_counter() - t0
-            run_cold.wall_el = wall_el
             return float(np.sum(span_ms)) * 1e-3, float(np.mean(span_ms))
+        run_cold.xch = float(np.mean([b.elapsed_time(c) for _, b, c in evs]))
+        el = float(np.sum([a.elapsed_time(c) for a, _, c in evs])) * 1e-3
+        return el, float(np.mean([a.elapsed_time(b) for a, b, _ in evs]))
+
+    def run_cold_wall():
         wall_el = 0.0
         for k in range(args.steps):
             evict()
@@ -1603,23 +1644,30 @@ def main() -> int:
             step()
             sync_barrier()
             wall_el += time.perf_counter() - t0
-        run_cold.wall_el = wall_el
-        run_cold.xch = float(np.mean([b.elapsed_time(c) for _, b, c in evs]))
-        el = float(np.sum([a.elapsed_time(c) for a, _, c in evs])) * 1e-3
-        return el, float(np.mean([a.elapsed_time(b) for a, b, _ in evs]))
-    run_cold.wall_el = 0.0
+        return wall_el
     run_cold.xch = run_warm.xch = 0.0
 
+    def dump():
+        if args.dump_outputs and rank == 0:  # every rank holds the assembled y
+            dump_outputs(args.dump_outputs, op.result().cpu().numpy())
+
+    cold_wall_el = el_o = kern_o = 0.0  # measured beside the headline with --full
     with torch.cuda.stream(stream):
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
         if args.cache == "cold":
             el, kern_ms = run_cold()
-            el_o, kern_o = run_warm()
+            dump()
+            if args.full:
+                cold_wall_el = run_cold_wall()
+                el_o, kern_o = run_warm()
         else:
             el, kern_ms = run_warm()
-            el_o, kern_o = run_cold()
+            dump()
+            if args.full:
+                el_o, kern_o = run_cold()
+                cold_wall_el = run_cold_wall()
     xch_ms = run_cold.xch if args.cache == "cold" else run_warm.xch
     rowsplit_beside = None
     if world == 1 and algo != sblas.ROWSPLIT and not args.no_rowsplit_beside:
@@ -1684,7 +1732,7 @@ def main() -> int:
             bound = orc.spmv_bound(rowptr, col_all, val_all, x_h, ALPHA, BETA, np.zeros(plan.m))
             check = bool(np.all(np.abs(y_dev - want) <= bound))
     stats_dev = dev if (dist is None or args.dist_backend == "nccl") else torch.device("cpu")
-    stats = torch.tensor([el, kern_ms, local_bytes, local_flops, el_o, kern_o, run_cold.wall_el, xch_ms,
+    stats = torch.tensor([el, kern_ms, local_bytes, local_flops, el_o, kern_o, cold_wall_el, xch_ms,
                           getattr(op, "plan_s", 0.0)],
                          dtype=torch.float64,
                          device=stats_dev)
@@ -1700,7 +1748,7 @@ def main() -> int:
         tot_bytes = float(sm[2])
     else:
         kern_ms_max, tot_bytes, kern_o_max = kern_ms, float(local_bytes), kern_o
-        cold_wall = run_cold.wall_el
+        cold_wall = cold_wall_el
         xch_max, plan_s_max = xch_ms, getattr(op, "plan_s", 0.0)
     ms_step = el / args.steps * 1e3
     total_flops = 2.0 * nnz
@@ -1752,24 +1800,25 @@ def main() -> int:
                      "csr_device_bytes_rank0": int(12 * local_nnz + 4 * (op.A.info()[0] + 1))},
             "exchange_ms_max_over_ranks": round(xch_max, 5),
             "timing": (("cold steps: device span of the SpMV call (events stamped by the runtime at "
-                        "its first kernel's start and last kernel's end, sblas_spmv_timed); host wall "
-                        "clock beside" if world == 1 else
+                        "its first kernel's start and last kernel's end, sblas_spmv_timed)" if world == 1 else
                         "cold steps: device time, HIP events on the launch stream from before the "
-                        "kernel to after exchange + merge, max over ranks; host wall clock beside")
+                        "kernel to after exchange + merge, max over ranks")
+                       + ("; host wall clock beside" if args.full else "")
                        if args.cache == "cold" else "warm: host wall clock over K back-to-back steps"),
             "cache": args.cache,
             "scrub": f"{args.scrub} {args.scrub_gib} GiB",
+        }
+        if args.full:
             # cold steps are timed on the device (run_cold); the host wall
             # clock around each, barrier round trips included, for comparison
-            "cold_host_wall_ms_per_step": round(cold_wall / args.steps * 1e3, 5),
-            ("warm" if args.cache == "cold" else "cold"): {
+            out["cold_host_wall_ms_per_step"] = round(cold_wall / args.steps * 1e3, 5)
+            out["warm" if args.cache == "cold" else "cold"] = {
                 "value": round(total_flops / (el_o / args.steps) / 1e9, 3),
                 "ms_per_step": round(el_o / args.steps * 1e3, 5),
                 "kernel_ms": round(kern_o, 5),
                 "kernel_ms_max_over_ranks": round(kern_o_max, 5),
                 "roofline_frac": round(local_bytes / (kern_o * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            },
-        }
+            }
         if world > 1 and args.dist_backend != "nccl":
             out["note"] = f"rehearsal: {world} ranks on {ndev} GPU(s) over {args.dist_backend}"
         out["topology"] = topo

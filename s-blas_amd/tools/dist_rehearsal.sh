@@ -13,7 +13,7 @@ for np in 2 3 4; do for combo in "allgather cyclic xsort panel rowsplit csr5" "a
   port=$((port+1))
   L=$O/rehearsal_${np}_${ex}_${part}_${algo}.log
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $np \
-    --master-addr 127.0.0.1 --master-port $port bench.py --gpus $np --dist-backend gloo \
+    --master-addr 127.0.0.1 --master-port $port bench.py --gpus $np --full --dist-backend gloo \
     --nrows 200000 --steps 3 --warmup 1 --check --exchange $ex --partition $part --algo $algo \
     > $L 2>&1 || { echo "FAIL np=$np $ex $part $algo"; tail -20 $L; exit 1; }
   grep -h '^{' $L | python3 -c "
@@ -22,7 +22,7 @@ d=json.loads(sys.stdin.read()); c=d.get('check_vs_oracle'); print('np=$np $ex $p
 done; done; done
 # torchrun with one rank over RCCL (the driver's N=1 launch shape)
 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-  --master-port $((port+1)) bench.py --gpus 1 --no-cpu-baseline --check --nrows 200000 > $O/rehearsal_1_nccl.log 2>&1 || exit 1
+  --master-port $((port+1)) bench.py --gpus 1 --full --no-cpu-baseline --check --nrows 200000 > $O/rehearsal_1_nccl.log 2>&1 || exit 1
 grep -h '^{' $O/rehearsal_1_nccl.log | cut -c1-200
 # SpMM (G2): rows of A by nnz, B replicated, C slices all-gathered
 for np in 2 3; do

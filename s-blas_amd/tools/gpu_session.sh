@@ -29,18 +29,18 @@ fi
 if [[ $STEP == all || $STEP == bench ]]; then
   run bench
   for a in panel rowsplit csr5; do for c in random prefix; do
-    timeout -k 10 300 python bench.py --algo $a --cols $c --no-cpu-baseline > $O/bench_${a}_${c}.log 2>&1 || exit 1
+    timeout -k 10 300 python bench.py --full --algo $a --cols $c --no-cpu-baseline > $O/bench_${a}_${c}.log 2>&1 || exit 1
   done; done
-  timeout -k 10 400 python bench.py > $O/bench_default.log 2>&1 || exit 1
+  timeout -k 10 400 python bench.py --full > $O/bench_default.log 2>&1 || exit 1
   grep -h '^{' $O/bench_*.log | cut -c1-400
 fi
 if [[ $STEP == all || $STEP == prof ]]; then
   run prof
   for a in panel rowsplit csr5; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$a -o run --output-format csv -- python bench.py --algo $a --no-cpu-baseline > $O/prof_$a.log 2>&1 || exit 1
-    timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch_$a -o run --output-format csv -- python bench.py --algo $a --no-cpu-baseline --steps 5 --warmup 1 > $O/pmc_fetch_$a.log 2>&1 || exit 1
-    timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_$a -o run --output-format csv -- python bench.py --algo $a --no-cpu-baseline --steps 5 --warmup 1 > $O/pmc_write_$a.log 2>&1 || exit 1
-    timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $O/pmc_l2_$a -o run --output-format csv -- python bench.py --algo $a --no-cpu-baseline --steps 5 --warmup 1 > $O/pmc_l2_$a.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$a -o run --output-format csv -- python bench.py --full --algo $a --no-cpu-baseline > $O/prof_$a.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_fetch_$a -o run --output-format csv -- python bench.py --full --algo $a --no-cpu-baseline --steps 5 --warmup 1 > $O/pmc_fetch_$a.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $O/pmc_write_$a -o run --output-format csv -- python bench.py --full --algo $a --no-cpu-baseline --steps 5 --warmup 1 > $O/pmc_write_$a.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $O/pmc_l2_$a -o run --output-format csv -- python bench.py --full --algo $a --no-cpu-baseline --steps 5 --warmup 1 > $O/pmc_l2_$a.log 2>&1 || exit 1
   done
   for a in panel rowsplit csr5; do
     case $a in panel) k=k_spmv_panel,k_panel_reduce;; rowsplit) k=k_spmv_rowsplit;; csr5) k=k_spmv_csr5,k_csr5_calibrate;; esac

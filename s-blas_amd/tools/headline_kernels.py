@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Average duration of the HEADLINE's kernels in a rocprofv3 kernel trace of
-`python bench.py` (run_kernel_trace.csv).  The default bench command also runs
+`python bench.py --full` (run_kernel_trace.csv).  That command also runs
 xsort on the structured stand-ins (the `structured` leg, after the headline),
 so the per-name stats csv mixes those launches into k_spmv_xsort's average;
 the headline's launches are the ones before the first launch of the row-split

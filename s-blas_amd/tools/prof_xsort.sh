@@ -5,7 +5,7 @@ set -o pipefail
 O=gpurun_out/pxs; mkdir -p $O
 export TMPDIR=/tmp
 V="$1"   # optional env assignments, e.g. "SBLAS_XS_ROWS=8192"
-B="bench.py --algo xsort --no-cpu-baseline --steps 5 --warmup 1"
+B="bench.py --full --algo xsort --no-cpu-baseline --steps 5 --warmup 1"
 env $V timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python $B > $O/trace.log 2>&1 || exit 1
 env $V timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python $B > $O/fetch.log 2>&1 || exit 1
 env $V timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE -d $O/write -o run --output-format csv -- python $B > $O/write.log 2>&1 || exit 1

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a rocprofv3 kernel trace of `python bench.py` into its phases
+"""Split a rocprofv3 kernel trace of `python bench.py --full` into its phases
 (warm-up, cold-timed, warm-timed, in launch order) and print per-phase mean
 durations of the SpMV kernels, so the trace can be compared with bench.py's
 HIP-event kernel_ms.  Usage: trace_split.py run_kernel_trace.csv [warmup steps]"""
@@ -17,7 +17,7 @@ def main():
     main_k = [r for r in rows if "k_spmv_" in r["Kernel_Name"] and "reduce" not in r["Kernel_Name"]]
     red = [r for r in rows if "reduce" in r["Kernel_Name"]]
     dur = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-    # bench.py order: warm-up, cold (events), cold (wall clock), warm
+    # bench.py --full order: warm-up, cold (events), cold (wall clock), warm
     phases = [("warmup", 0, warm_up), ("cold_events", warm_up, warm_up + steps),
               ("cold_wall", warm_up + steps, warm_up + 2 * steps),
               ("warm", warm_up + 2 * steps, warm_up + 3 * steps)]

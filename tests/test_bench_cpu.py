@@ -96,7 +96,7 @@ def test_config3_object_keys():
 
 
 def test_config3_is_on_by_default():
-    """Both drivers add the configs[2] leg unless --no-config3 is given."""
+    """Both drivers add the configs[2] leg (--full) unless --no-config3 is given."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.count('out["config3"] = config3') == 2
     assert src.count("if not args.no_config3:") == 2
@@ -126,7 +126,7 @@ def test_config4_config5_object_keys():
 
 
 def test_config4_config5_on_by_default():
-    """Both drivers add the configs[3] / configs[4] legs unless switched off."""
+    """Both drivers add the configs[3] / configs[4] legs (--full) unless switched off."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert src.count('out["config4"] = config4') == 2 and src.count('out["config5"] = config5') == 2
     assert src.count("if not args.no_config4:") == 2 and src.count("if not args.no_config5:") == 2
@@ -218,6 +218,22 @@ def test_every_leg_carries_cpu_baseline_and_check(monkeypatch):
     assert "args.check = not args.no_check" in src
     assert src.count('out["check_vs_oracle"] = check') == 2
     assert src.count("        attach_cpu_baselines(out, args)") == 2
+
+
+def test_dump_outputs_writes_y_and_samples_large(tmp_path, monkeypatch):
+    """--dump-outputs: DIR/y.npy is the float64 y as given; above the byte cap
+    it is the same ascending seeded sample on every call."""
+    import numpy as np
+    y = np.random.default_rng(1).random(1000)
+    bench.dump_outputs(str(tmp_path / "a"), y)
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 100)
+    bench.dump_outputs(str(tmp_path / "b"), y)
+    bench.dump_outputs(str(tmp_path / "c"), y + 1.0)
+    b, c = np.load(tmp_path / "b" / "y.npy"), np.load(tmp_path / "c" / "y.npy")
+    assert b.shape == (100,) and np.array_equal(c, b + 1.0)  # the same entries of both
+    assert np.isin(b, y).all() and len(set(b)) == 100
 
 
 def test_topology_object_keys():

@@ -27,8 +27,8 @@ CONFIG3_KEYS = ("kernel_ms_max", "exchange_ms_max", "step_ms", "gflops", "roofli
 ])
 def test_bench_ctx_driver(algo, partition, exchange):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--driver", "ctx", "--check",
-           "--nrows", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--algo", algo,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--driver", "ctx", "--full",
+           "--check", "--nrows", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--algo", algo,
            "--partition", partition, "--exchange", exchange]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -68,8 +68,8 @@ def test_bench_ctx_loopback(gpus, algo, partition, exchange):
     next step's y and the per-device timing all run and are checked against
     the oracle; every rank's y must be bit-identical."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--ctx-loopback", "--check",
-           "--nrows", "200000", "--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--algo", algo,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--ctx-loopback", "--full",
+           "--check", "--nrows", "200000", "--steps", "2", "--warmup", "2", "--no-cpu-baseline", "--algo", algo,
            "--partition", partition, "--exchange", exchange]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -93,7 +93,7 @@ def test_bench_ctx_loopback(gpus, algo, partition, exchange):
 
 
 def test_bench_ctx_loopback_full_config3():
-    """`bench.py --gpus 8 --ctx-loopback --check` on the
+    """`bench.py --gpus 8 --ctx-loopback --full --check` on the
     FULL n = 2e6 matrix (39.75M nnz): the default leg (cyclic chunks, the
     library's kernel per slice, all-gather + placement) and the configs[2]
     leg (CSR5 on the nnz split, all-reduce of the zero-padded y) both checked
@@ -101,8 +101,8 @@ def test_bench_ctx_loopback_full_config3():
     bit-identical.  8 context ranks share the box's GPU (loopback
     collectives); the first 8-GPU run executes the same code with RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--ctx-loopback", "--check",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--ctx-loopback", "--full",
+           "--check", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -119,11 +119,49 @@ def test_bench_ctx_loopback_overlap(gpus, parts):
     """`bench.py --gpus N --overlap K` through the ctx driver (loopback): the
     exchange overlapped over K parts of every rank's chunks, checked."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--ctx-loopback", "--check",
-           "--nrows", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-config3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--ctx-loopback", "--full",
+           "--check", "--nrows", "200000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-config3",
            "--overlap", str(parts)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["check_vs_oracle"] is True, line
     assert line["config"]["overlap_parts"] == parts
+
+
+@pytest.mark.parametrize("driver", ["auto", "ctx"])
+def test_bench_plain_run_is_the_headline_only(driver, tmp_path, sb, orc):
+    """Without --full a run times its steps and prints the headline line
+    alone: no other cache mode, check, leg or CPU baseline.  --dump-outputs
+    writes the y the last timed step left: y_k = alpha*A*x + beta*y_(k-1) from
+    y_0 = 0 over warmup + steps calls, compared with the oracle's iteration
+    under the per-row fp64 bound carried along (tol_k = bound(y_(k-1)) +
+    beta*tol_(k-1))."""
+    import numpy as np
+    import bench
+    n, steps, warmup = 200_000, 3, 1
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+           str(warmup), "--nrows", str(n), "--driver", driver, "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == bench.METRIC and line["unit"] == "GFLOP/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["steps"] == steps and line["cache"] == "cold"
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - 2.0 * line["config"]["nnz"] / (line["ms_per_step"] * 1e-3) / 1e9) < 1e-2 * line["value"]
+    for k in ("warm", "cold_host_wall_ms_per_step", "check_vs_oracle", "rowsplit_beside", "deterministic_beside",
+              "config3", "config4", "config5", "structured", "measured_peak", "cpu_baseline"):
+        assert k not in line, k
+    got = np.load(tmp_path / "y.npy")
+    assert got.dtype == np.float64 and got.shape == (n,)
+    rp = sb.gen_synth_rowptr(n)
+    col, val = sb.gen_synth_rows(n, rp, 0, n)
+    x = sb.gen_vector(n, 43)
+    want, tol = np.zeros(n), np.zeros(n)
+    for _ in range(warmup + steps):
+        tol = orc.spmv_bound(rp, col, val, x, bench.ALPHA, bench.BETA, want) + bench.BETA * tol
+        want = orc.csr_spmv(rp, col, val, x, bench.ALPHA, bench.BETA, want)
+    assert np.all(np.abs(got - want) <= tol), float(np.max(np.abs(got - want) - tol))

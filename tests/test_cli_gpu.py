@@ -178,7 +178,7 @@ def bench_2rank(extra, nrows=2_000_000):
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
             "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
             os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-            "--dist-backend", "gloo", "--check", "--no-cpu-baseline", "--nrows", str(nrows)] + extra
+            "--dist-backend", "gloo", "--full", "--check", "--no-cpu-baseline", "--nrows", str(nrows)] + extra
     rc, out, err = run(args, timeout=110)
     assert rc == 0, out[-3000:] + err[-3000:]
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
@@ -238,7 +238,7 @@ def test_torchrun_8_ranks_full_size():
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
             "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
             os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1",
-            "--dist-backend", "gloo", "--check", "--no-cpu-baseline"]
+            "--dist-backend", "gloo", "--full", "--check", "--no-cpu-baseline"]
     rc, out, err = run(args, timeout=115)
     assert rc == 0, out[-3000:] + err[-3000:]
     line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
