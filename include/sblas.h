@@ -181,16 +181,36 @@ int sblas_csr_set_deterministic(sblas_csr A, int on);
  * items, grid (persistent workgroups), solo (power-law layout), 256-entry
  * chunks, most chunks of one item.  For tools and tests. */
 int sblas_csr_xsort_info(sblas_csr A, long long *info);
+/* Copies one buffer of the analysed XSORT plan to the host, for tools and
+ * tests (XSORT's default y is not bitwise repeatable, so the layout itself
+ * must be comparable).  what: 0 = the chunk storage (keys and values, chunks
+ * x 3072 B), 1 = the item records, 2 = the wide ranges' records, 3 = the 32
+ * initial claim heads (as the build armed them; launches advance and re-arm
+ * the resident ones).  *bytes receives the buffer's size; host_buf == NULL
+ * only sizes; cap_bytes below the size is SBLAS_ERR_INVALID.  Waits for the
+ * device. */
+int sblas_csr_xsort_export(sblas_csr A, int what, void *host_buf, long long cap_bytes, long long *bytes);
+/* How the resident XSORT layout was built (4 values): 1.0 if on the device
+ * (the default: a stable radix sort of the entries by (row range, column)
+ * and a fill pass; only the block offsets come back to the host), 0.0 if on
+ * the host (test hook "xs_hostplan", or the fallback when the device build's
+ * scratch of ~24 B per entry does not fit); build seconds (wall, analysis
+ * entry to ready); peak scratch bytes of the build; bytes copied device ->
+ * host during the build.  Both builds give the same bytes. */
+int sblas_csr_xsort_build_info(sblas_csr A, double *info);
 int sblas_csr_get_deterministic(sblas_csr A, int *on);
 /* XCD column panels the analysed plan of `algo` runs over (0: the plain
- * layout / not analysed).  ROWSPLIT and CSR5 build per-panel plans (P = 4
- * on config 2) on large scattered-column matrices (x > 8 MiB, nnz >= 2M, most
- * sampled rows span > n/4 of the columns; test hooks "rs_panel" /
- * "csr5_panel" force either form); PANEL always does (unless only one panel
+ * layout / not analysed).  ROWSPLIT and CSR5 build per-panel plans on large
+ * scattered-column matrices (x > 8 MiB, nnz >= 2M, most sampled rows span
+ * > n/4 of the columns; test hooks "rs_panel" / "csr5_panel" force either
+ * form): ROWSPLIT P = 4 on config 2, CSR5 twice as many (at most 8) from 32M
+ * entries, i.e. P = 8 on config 2.  PANEL always does (unless only one panel
  * holds entries). */
 int sblas_csr_panels(sblas_csr A, int algo, int *panels);
 /* Device bytes held by the analysis of `algo` (free memory before - after
- * sblas_csr_analyse; 0 if not analysed): the layout's cost beside the CSR. */
+ * sblas_csr_analyse; XSORT: the sum of its plan's allocations, the same for
+ * the device and the host build; 0 if not analysed): the layout's cost
+ * beside the CSR. */
 long long sblas_csr_plan_bytes(sblas_csr A, int algo);
 /* bytes the algorithm must move per call (DESIGN.md "Algorithmic bytes"). */
 long long sblas_spmv_algorithmic_bytes(sblas_csr A, int beta_nonzero);
@@ -526,8 +546,13 @@ int sblas_peer_refs(int a, int b);
 /* Planner override for tests (set = 0 clears it), read when a plan is built:
  * "xs_cap" (xsort work per item: small values give many items, exercising the
  * dynamic claims on small matrices), "xs_allwide" (0/1), "xs_solo" (0/1),
- * "spmm_ctile" (0/1: C-tile form), "spmm_mfma_fill" (MFMA tile threshold),
- * "rs_panel" / "csr5_panel" (0/1: XCD-panel forms), "panels" (panel count).
+ * "xs_hostplan" (non-zero: the xsort layout is built on the host -- the
+ * reference form the default device build is pinned to byte for byte),
+ * "xs_devplan_nomem" (non-zero: the device build's scratch allocation fails,
+ * so the host fallback runs), "csr5_hostplan" (non-zero: the CSR5 tile
+ * descriptors are built on the host), "spmm_ctile" (0/1: C-tile form),
+ * "spmm_mfma_fill" (MFMA tile threshold), "rs_panel" / "csr5_panel" (0/1:
+ * XCD-panel forms), "panels" (panel count).
  * Process-wide; production code never sets them. */
 int sblas_test_set_option(const char *name, double value, int set);
 

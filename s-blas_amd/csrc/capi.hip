@@ -418,6 +418,53 @@ int sblas_csr_xsort_info(sblas_csr A, long long *info)
     return SBLAS_OK;
 }
 
+int sblas_csr_xsort_export(sblas_csr A, int what, void *host_buf, long long cap_bytes, long long *bytes)
+{
+    if (!A || !bytes || what < 0 || what > 3) return SBLAS_ERR_INVALID;
+    const XsPlan &P = A->xs;
+    if (!P.ready) {
+        set_error("sblas_csr_xsort_export: no analysed XSORT plan");
+        return SBLAS_ERR_INVALID;
+    }
+    DeviceGuard g(A->device);
+    int heads[32];
+    const void *src = nullptr;
+    long long nb = 0;
+    switch (what) {
+    case 0: src = P.key; nb = P.nchunks * 3072LL; break;
+    case 1: src = P.xrec; nb = P.xrec_bytes; break;
+    case 2: src = P.wranges; nb = (long long)sizeof(XsRange) * P.nwide; break;
+    default:  // as the build armed them: both parities start past the static items
+        for (int k = 0; k < 32; ++k) heads[k] = (k & 15) < 8 ? P.qstat[k & 15] : 0;
+        nb = (long long)sizeof(heads);
+        break;
+    }
+    *bytes = nb;
+    if (!host_buf) return SBLAS_OK;
+    if (cap_bytes < nb) {
+        set_error("sblas_csr_xsort_export: buffer of %lld bytes, %lld needed", cap_bytes, nb);
+        return SBLAS_ERR_INVALID;
+    }
+    if (what == 3) {
+        memcpy(host_buf, heads, sizeof(heads));
+        return SBLAS_OK;
+    }
+    SBLAS_HIP(hipDeviceSynchronize());
+    if (nb) SBLAS_HIP(hipMemcpy(host_buf, src, (size_t)nb, hipMemcpyDeviceToHost));
+    return SBLAS_OK;
+}
+
+int sblas_csr_xsort_build_info(sblas_csr A, double *info)
+{
+    if (!A || !info) return SBLAS_ERR_INVALID;
+    const XsPlan &P = A->xs;
+    info[0] = P.ready && P.dev_built ? 1.0 : 0.0;
+    info[1] = P.build_s;
+    info[2] = (double)P.scratch_bytes;
+    info[3] = (double)P.d2h_bytes;
+    return SBLAS_OK;
+}
+
 int sblas_csr_pick(sblas_csr A, void *stream, int *algo)
 {
     if (!A || !algo) return SBLAS_ERR_INVALID;

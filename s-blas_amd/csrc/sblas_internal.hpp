@@ -233,6 +233,12 @@ struct XsPlan {
     long long nchunks = 0;       // 256-entry chunks (blocks padded to whole chunks)
     bool solo = false;           // narrow ranges are items of their own (16,384 LDS rows)
     int maxc = 0;                // most chunks of one item (both sub-items)
+    // how the resident layout was built (sblas_csr_xsort_build_info)
+    bool dev_built = false;      // on the device (xsort.hip xs_layout_device), else on the host
+    double build_s = 0.0;        // wall seconds, build_xsort_plan entry to ready
+    long long scratch_bytes = 0; // device temporaries of the build (freed again)
+    long long d2h_bytes = 0;     // bytes the build copied device -> host
+    long long xrec_bytes = 0;    // size of xrec
     bool ready = false;
 };
 
@@ -345,8 +351,11 @@ bool peer_denied();  // the test hook's state
 
 // Test hooks (capi.hip): a planner override set by sblas_test_set_option;
 // false when unset.  Names: "xs_cap", "xs_allwide", "xs_solo" (xsort
-// planner), "spmm_ctile", "spmm_mfma_fill" (SpMM plan form), "rs_panel",
-// "csr5_panel", "panels" (XCD-panel forms).
+// planner), "xs_hostplan" (xsort layout built on the host), "xs_devplan_nomem"
+// (its device build's scratch allocation fails: the host fallback),
+// "csr5_hostplan" (CSR5 descriptors built on the host), "spmm_ctile",
+// "spmm_mfma_fill" (SpMM plan form), "rs_panel", "csr5_panel", "panels"
+// (XCD-panel forms).
 bool test_option(const char *name, double *value);
 
 // Host helpers shared by capi / refapi (host_utils.cpp).

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -120,6 +120,8 @@ _sig("sblas_test_set_option", _i, C.c_char_p, _d, _i)
 _sig("sblas_csr_set_deterministic", _i, _p, _i)
 _sig("sblas_csr_xsort_info", _i, _p, _p)
 _sig("sblas_csr_get_deterministic", _i, _p, _p)
+_sig("sblas_csr_xsort_export", _i, _p, _i, _p, _ll, _p)
+_sig("sblas_csr_xsort_build_info", _i, _p, _p)
 _sig("sblas_ctx_create", _i, _p, _i, _p)
 _sig("sblas_ctx_destroy", _i, _p)
 _sig("sblas_ctx_ngpu", _i, _p, _p)
@@ -480,6 +482,13 @@ def spmv_mgpu(version: str, m, n, rowptr, col, val, x, y, alpha, beta, ngpu=1, k
 # --------------------------------------------------------------------------
 # persistent device objects
 # --------------------------------------------------------------------------
+class XsortBuildInfo(NamedTuple):
+    device_built: int    # 1: the layout was built on the device, 0: on the host
+    build_s: float       # wall seconds, analysis entry to ready
+    scratch_bytes: int   # device temporaries of the build (freed again)
+    d2h_bytes: int       # bytes the build copied device -> host
+
+
 class DeviceCSR:
     """A CSR slice resident on one GPU (sblas_csr handle)."""
 
@@ -499,6 +508,16 @@ class DeviceCSR:
     def upload(cls, device: int, n: int, rowptr, col, val, stream=None):
         m = len(rowptr) - 1
         return cls.upload_slice(device, n, rowptr, col, val, 0, m, 0, int(rowptr[-1]), stream)
+
+    @classmethod
+    def from_device(cls, device: int, m: int, n: int, nnz: int, rowptr_ptr: int, col_ptr: int,
+                    val_ptr: int, stream=None):
+        """A handle over a copy of device arrays (sblas_csr_from_device): int32
+        rowptr [m+1] / col [nnz], float64 val [nnz], given as addresses."""
+        h = C.c_void_p()
+        check(lib.sblas_csr_from_device(C.byref(h), device, m, n, nnz, rowptr_ptr, col_ptr, val_ptr,
+                                        stream), "csr_from_device")
+        return cls(h.value)
 
     def info(self) -> Tuple[int, int, int]:
         m, n, nnz = C.c_int(), C.c_int(), C.c_longlong()
@@ -542,6 +561,24 @@ class DeviceCSR:
         check(lib.sblas_csr_xsort_info(self.h, ptr(v)), "csr_xsort_info")
         keys = ("ready", "ranges", "wide", "items", "grid", "solo", "chunks", "max_item_chunks")
         return {k: int(x) for k, x in zip(keys, v)}
+
+    def xsort_export(self, what: int) -> np.ndarray:
+        """One buffer of the analysed XSORT plan as bytes (sblas_csr_xsort_export):
+        0 chunk storage, 1 item records, 2 wide-range records, 3 the 32
+        initial claim heads."""
+        nb = C.c_longlong()
+        check(lib.sblas_csr_xsort_export(self.h, what, None, 0, C.byref(nb)), "csr_xsort_export")
+        buf = np.zeros(max(nb.value, 1), np.uint8)
+        check(lib.sblas_csr_xsort_export(self.h, what, ptr(buf), nb.value, C.byref(nb)),
+              "csr_xsort_export")
+        return buf[:nb.value]
+
+    def xsort_build_info(self) -> "XsortBuildInfo":
+        """How the resident XSORT layout was built (sblas_csr_xsort_build_info):
+        (device_built 0/1, build_s, scratch_bytes, d2h_bytes)."""
+        v = np.zeros(4, np.float64)
+        check(lib.sblas_csr_xsort_build_info(self.h, ptr(v)), "csr_xsort_build_info")
+        return XsortBuildInfo(int(v[0]), float(v[1]), int(v[2]), int(v[3]))
 
     @property
     def deterministic(self) -> bool:
