@@ -181,6 +181,26 @@ int sblas_csr_set_deterministic(sblas_csr A, int on);
  * items, grid (persistent workgroups), solo (power-law layout), 256-entry
  * chunks, most chunks of one item.  For tools and tests. */
 int sblas_csr_xsort_info(sblas_csr A, long long *info);
+/* The XSORT planner alone, for inspection and tests: what it decides for a
+ * matrix of m rows (host rowptr, int64, m + 1 ascending 32-bit offsets) and n
+ * columns on a device holding `resident` workgroups at once (a plan build
+ * passes its CU count x the kernel's occupancy, 1).  Needs no GPU and no
+ * handle; the same arguments always give the same plan.  Overrides: cap
+ * (NULL: searched; else the fixed sub-item cost of "xs_cap"), allwide and
+ * solo (0 / 1, -1: the planner decides).  info[27]: q, G, Wg, solo, ranges,
+ * wide ranges, items, grid, dynamic (items beyond the static share), qstride,
+ * partial_len (sum of 8 * nrows over the wide ranges), then qlen[8] and
+ * qstat[8] (items per XCD queue, and how many of them block b = 8j + k takes
+ * statically).  ranges == NULL / items == NULL only sizes; else ranges
+ * receives 5 values per range (row0, nrows, wide, widx, pbase; ranges_cap
+ * counts ranges) and items 2 per item, queue by queue (sub0, sub1: sub =
+ * range << 8 | k, k = 0 a narrow range, 1..8 the wide sub-item of XCD k - 1,
+ * -1 none; items_cap counts items).  A null rowptr or info, m < 0 or too
+ * little room is SBLAS_ERR_INVALID; n beyond 127 column groups
+ * SBLAS_ERR_UNSUPPORTED. */
+int sblas_xsort_plan_host(int m, int n, const long long *rowptr, int resident, const double *cap,
+                          int allwide, int solo, long long *info, long long *ranges, long long ranges_cap,
+                          int *items, long long items_cap);
 /* Copies one buffer of the analysed XSORT plan to the host, for tools and
  * tests (XSORT's default y is not bitwise repeatable, so the layout itself
  * must be comparable).  what: 0 = the chunk storage (keys and values, chunks

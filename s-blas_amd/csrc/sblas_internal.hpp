@@ -6,10 +6,12 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/sblas.h"
+#include "xsort.hpp"
 
 namespace sblas {
 
@@ -182,7 +184,9 @@ struct SpmmPlan {
     bool ready = false;
 };
 
-// Column-sorted XCD-group plan (algo 5, xsort.hip).  Columns are cut into
+// Column-sorted XCD-group plan (algo 5: the planner in xsort_plan.cpp, the
+// layout builders in xsort_layout.hip, the kernel and the plan build in
+// xsort.hip; their shared constants and XsRange in xsort.hpp).  Columns are cut into
 // G = 8q groups of Wg <= 2^18 columns (XCD k serves groups [kq, (k+1)q)), rows
 // into ranges of <= kXsRows rows.  Block (range i, group g) holds the range's
 // entries of group g sorted by (column, row) as packed keys
@@ -192,14 +196,6 @@ struct SpmmPlan {
 // and writes y); a wide range is 8 sub-items, one per XCD, each writing an
 // alpha-free partial that a reduce pass adds in XCD order.  A work item pairs
 // two sub-items (one per half of the workgroup).
-struct XsRange {
-    int row0;
-    int nrows;
-    int wide;
-    int widx;         // wide: index among the wide ranges, else -1
-    long long pbase;  // wide: offset of the range's [8][nrows] partials
-};
-
 struct XsArgs {
     const uint32_t *key;
     const double *val;
@@ -221,7 +217,7 @@ struct XsPlan {
     XsRange *wranges = nullptr;  // [nwide] the wide ranges' records (k_xsort_reduce)
     uint32_t *key = nullptr;     // owns the chunk storage (keys and values, interleaved per chunk)
     double *val = nullptr;       // values inside it
-    int kstride = 64, vstride = 128;
+    int kstride = 192, vstride = 192;  // 16-B units of a chunk (kXsChunkBytes / 16)
     long long *xrec = nullptr;   // item records (see XsArgs)
     int *qhead = nullptr;        // [2][16]: claim heads per launch parity
     mutable int parity = 0;      // flips every launch (stream-ordered launches)
@@ -234,7 +230,7 @@ struct XsPlan {
     bool solo = false;           // narrow ranges are items of their own (16,384 LDS rows)
     int maxc = 0;                // most chunks of one item (both sub-items)
     // how the resident layout was built (sblas_csr_xsort_build_info)
-    bool dev_built = false;      // on the device (xsort.hip xs_layout_device), else on the host
+    bool dev_built = false;      // on the device (xsort_layout.hip xs_layout_device), else on the host
     double build_s = 0.0;        // wall seconds, build_xsort_plan entry to ready
     long long scratch_bytes = 0; // device temporaries of the build (freed again)
     long long d2h_bytes = 0;     // bytes the build copied device -> host
@@ -312,6 +308,13 @@ int launch_spmv_xsort(const sblas_csr_s &A, double alpha, const double *x,
                       double beta, double *y, hipStream_t s);
 int build_xsort_plan(sblas_csr_s &A, hipStream_t s);
 void free_xsort_plan(sblas_csr_s &A);
+// the layout builders (xsort_layout.hip): blk[] and the chunk storage of the
+// planner's ranges.  The device build sets on_device = false when it could
+// not run (scratch does not fit): nothing was published, the host build runs.
+int xs_layout_device(sblas_csr_s &A, const std::vector<XsRange> &ranges, int rows_cap, int nrows_cap,
+                     hipStream_t s, std::vector<long long> &blk, bool &on_device);
+int xs_layout_host(sblas_csr_s &A, const std::vector<XsRange> &ranges, int rows_cap, int nrows_cap,
+                   std::vector<long long> &blk, std::unique_ptr<unsigned char[]> &hbuf);
 
 int build_spmm_plan(sblas_csr_s &A, int ncols, hipStream_t s);  // C width of the first call
 void free_spmm_plan(sblas_csr_s &A);
@@ -350,8 +353,10 @@ void peer_release(int a, int b);
 bool peer_denied();  // the test hook's state
 
 // Test hooks (capi.hip): a planner override set by sblas_test_set_option;
-// false when unset.  Names: "xs_cap", "xs_allwide", "xs_solo" (xsort
-// planner), "xs_hostplan" (xsort layout built on the host), "xs_devplan_nomem"
+// false when unset.  Names: "xs_cap", "xs_allwide", "xs_solo" (xsort planner:
+// build_xsort_plan reads them into XsPlanOptions, the planner itself never
+// looks), "xs_hostplan" (xsort layout built on the host; read there too: the
+// fourth option of the plan build), "xs_devplan_nomem"
 // (its device build's scratch allocation fails: the host fallback),
 // "csr5_hostplan" (CSR5 descriptors built on the host), "spmm_ctile",
 // "spmm_mfma_fill" (SpMM plan form), "rs_panel", "csr5_panel", "panels"

@@ -29,9 +29,9 @@
 // rate while gather j of a wave covers the 64 consecutive entries 64j..64j+63.
 // Keys pack (col - g*Wg) << 14 | (row - row0); a padding key has the column
 // field all ones (no real column reaches it) and row 0.  The layout is built
-// on the device (xs_layout_device below: one stable radix sort of the entries
-// by (range, column) and a fill pass); the host build is kept as its
-// byte-identical reference and fallback.
+// on the device (xs_layout_device in xsort_layout.hip: one stable radix sort
+// of the entries by (range, column) and a fill pass); the host build is kept
+// as its byte-identical reference and fallback.
 //
 // Work: a narrow range (short rows) is one sub-item -- it walks all G groups,
 // starting at its XCD's first group and wrapping, and writes y; a wide range
@@ -48,12 +48,13 @@
 // own sub-item continues on its partner's and both halves end together.
 // Matrices with many empty rows (power-law graphs) run their narrow ranges
 // as solo items: both teams on one range of up to 16,384 LDS rows.
+//
+// Files: this one holds the kernels, the plan build and the launch; the
+// planner (which ranges, which items in which queue) is xs_plan_host in
+// xsort_plan.cpp, plain host code; the layout builders are in
+// xsort_layout.hip; xsort.hpp holds what the three share.
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
-#include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <memory>
 #include <utility>
 #include <vector>
@@ -62,29 +63,19 @@
 
 namespace sblas {
 
+// Workgroup: two 4-wave teams (512 threads, 2 waves per SIMD, up to 256
+// VGPRs a wave) -- the register budget lets the compiler keep more of the
+// stream in flight than two 8-wave teams (1024 threads, 128 VGPRs) or two
+// 6-wave teams (768, ~170): config 2 N = 1 / 2 / 4 / 8 150.6-152.5 /
+// 96.4-96.7 / 65.5-65.6 / 40.7-40.8 us against 153.0-153.3 / 99.1 /
+// 66.3-66.9 / 42.1-42.5, 27-point 128^3 117 vs 121, 7-point 160^3 83 vs
+// 85, R-MAT equal (profiles/r05/wg512p/).
 constexpr int kXsThreads = 512;   // two teams of kXsWaves waves
 constexpr int kXsWaves = 4;       // waves per team
 constexpr int kXsTeam = kXsWaves * 64;
 constexpr int kXsU = 2;           // chunks per dynamic claim
-constexpr long long kXsAllWideMaxNnz = 6000000;  // all ranges wide up to this many entries (planner)
-// LDS row accumulators per workgroup: 16384 = 128 KiB (default); an
-// experiment build may raise it towards the 160 KiB of a gfx950 CU
-// (SBLAS_XS_LDS_ROWS=19456: 152 KiB of rows + ~6 KiB of bookkeeping)
-#ifndef SBLAS_XS_LDS_ROWS
-#define SBLAS_XS_LDS_ROWS 16384
-#endif
-constexpr int kXsRows = SBLAS_XS_LDS_ROWS;
-static_assert(kXsRows % 512 == 0, "two teams of whole 256-row blocks");
-constexpr int kXsHalfRows = kXsRows / 2;
-constexpr int kXsRowBits = 14;     // packed key: local row in the low 14 bits
-constexpr int kXsColBits = 18;     //             group-local column above
-constexpr int kXsChunk = 256;      // entries per chunk: one wave, 4 per lane
-constexpr uint32_t kXsPad = ((1u << kXsColBits) - 1) << kXsRowBits;  // column all ones, row 0
-static_assert(kXsRowBits + kXsColBits == 32, "packed key is 32 bits");
-static_assert(kXsHalfRows <= (1 << kXsRowBits), "a team's local row must fit the key");
-// a range's rows: a team's half, or (solo items) the whole workgroup's
-// accumulators up to what the key's row field addresses
-constexpr int kXsItemRows = kXsRows < (1 << kXsRowBits) ? kXsRows : (1 << kXsRowBits);
+// (the row / key / chunk constants shared with the planner and the layout
+// builders are in xsort.hpp)
 
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
@@ -445,683 +436,38 @@ void free_xsort_plan(sblas_csr_s &A)
     A.xs = XsPlan{};
 }
 
-// ---- the layout (inspector) --------------------------------------------------
-// Both builders produce the same bytes: blk[] (I*G + 1 chunk offsets) and the
-// chunk storage.  ranges[] come from the planner (build_xsort_plan).
-constexpr size_t kXsChunkBytes = (size_t)kXsChunk * (sizeof(uint32_t) + sizeof(double));
-static const char *const kXsBadMsg = "xsort: column index out of [0, n) or key overflow";
-
-// Host build (the reference form; test hook "xs_hostplan", and the fallback
-// when the device build's scratch does not fit): copies col / val to the
-// host, buckets and stable-sorts every block under OpenMP, fills hbuf.
-static int xs_layout_host(sblas_csr_s &A, const std::vector<XsRange> &ranges, int rows_cap, int nrows_cap,
-                          std::vector<long long> &blk, std::unique_ptr<unsigned char[]> &hbuf)
-{
-    XsPlan &P = A.xs;
-    const int n = A.n, G = P.G, Wg = P.Wg, I = (int)ranges.size();
-    const long long nnz = A.nnz;
-    const long long wmax = (1LL << kXsColBits) - 1;
-    const std::vector<int> &rp = A.h_rowptr;
-    // host copies of the CSR entries (uninitialised: the copies fill them)
-    std::unique_ptr<int[]> hcol(new int[(size_t)std::max<long long>(nnz, 1)]);
-    std::unique_ptr<double[]> hval(new double[(size_t)std::max<long long>(nnz, 1)]);
-    if (nnz) {
-        SBLAS_HIP(hipMemcpy(hcol.get(), A.col, sizeof(int) * nnz, hipMemcpyDeviceToHost));
-        SBLAS_HIP(hipMemcpy(hval.get(), A.val, sizeof(double) * nnz, hipMemcpyDeviceToHost));
-        P.d2h_bytes += (long long)(sizeof(int) + sizeof(double)) * nnz;
-    }
-
-    // pass 1: every block (range, group) bucketed and sorted by (column, row)
-    // once, kept for the fill.  One range per task for the bucketing (a wide
-    // range holds ~13x a narrow one's entries, and they sit together at the
-    // heavy rows), then the blocks are sorted as tasks of their own.
-    const size_t nblk = (size_t)I * G;
-    std::vector<std::vector<std::pair<uint32_t, double>>> bk(nblk);
-    bool bad = false;
-#pragma omp parallel for schedule(dynamic, 1) reduction(|| : bad)
-    for (int i = 0; i < I; ++i) {
-        const XsRange &R = ranges[i];
-        std::vector<int> cnt(G, 0);
-        for (int e = rp[R.row0]; e < rp[R.row0 + R.nrows]; ++e) {
-            const int c = hcol[e];
-            if (c >= 0 && c < n) ++cnt[c / Wg];
-        }
-        for (int g = 0; g < G; ++g) bk[(size_t)i * G + g].reserve(cnt[g]);
-        for (int r = R.row0; r < R.row0 + R.nrows; ++r) {
-            for (int e = rp[r]; e < rp[r + 1]; ++e) {
-                const int c = hcol[e];
-                if (c < 0 || c >= n) {
-                    bad = true;
-                    continue;
-                }
-                const int g = c / Wg;
-                const uint32_t cp = (uint32_t)(c - g * Wg), lr = (uint32_t)(r - R.row0);
-                if ((long long)cp >= wmax || lr >= (uint32_t)(R.wide ? rows_cap : nrows_cap)) bad = true;
-                bk[(size_t)i * G + g].push_back({(cp << kXsRowBits) | lr, hval[e]});
-            }
-        }
-    }
-#pragma omp parallel for schedule(dynamic, 4)
-    for (long long k = 0; k < (long long)nblk; ++k) {
-        auto &bb = bk[(size_t)k];
-        std::stable_sort(bb.begin(), bb.end(),
-                         [](const std::pair<uint32_t, double> &u, const std::pair<uint32_t, double> &v) {
-                             return u.first < v.first;
-                         });
-    }
-    if (bad) {
-        set_error("%s", kXsBadMsg);
-        return SBLAS_ERR_INVALID;
-    }
-    blk.assign(nblk + 1, 0);
-    for (size_t k = 0; k < nblk; ++k)
-        blk[k + 1] = blk[k] + ((long long)bk[k].size() + kXsChunk - 1) / kXsChunk;
-    const long long nchunks = blk.back();
-
-    // pass 2: fill every chunk (lane-transposed, header comment).  Every byte
-    // of every chunk is written by the fill below: no zeroing pass.
-    const size_t cbytes = kXsChunkBytes;
-    const size_t hb_n = (size_t)std::max<long long>(nchunks, 1) * cbytes;
-    hbuf.reset(new unsigned char[hb_n]);
-    auto chunk_keys = [&](long long c) { return (uint32_t *)(hbuf.get() + (size_t)c * cbytes); };
-    auto chunk_vals = [&](long long c) {
-        return (double *)(hbuf.get() + (size_t)c * cbytes + kXsChunk * sizeof(uint32_t));
-    };
-#pragma omp parallel for schedule(dynamic, 64)
-    for (long long k = 0; k < (long long)nblk; ++k) {
-        const auto &bb = bk[(size_t)k];
-        const long long c0 = blk[(size_t)k], c1 = blk[(size_t)k + 1];
-        for (long long c = c0; c < c1; ++c) {
-            uint32_t *kc = chunk_keys(c);
-            double *vc = chunk_vals(c);
-            for (int p = 0; p < kXsChunk; ++p) {
-                const long long src = (c - c0) * kXsChunk + p;
-                const bool in = src < (long long)bb.size();
-                const int l = p & 63, j = p >> 6;
-                kc[4 * l + j] = in ? bb[src].first : kXsPad;
-                vc[(j < 2 ? 0 : 128) + 2 * l + (j & 1)] = in ? bb[src].second : 0.0;
-            }
-        }
-    }
-    return SBLAS_OK;
-}
-
-// Device build.  A range's entries are a contiguous span of the CSR arrays in
-// (row, position) order, and block (i, g) is that span's entries of group g
-// stably sorted by group-local column: the whole layout is ONE stable sort of
-// the entries, taken in CSR order, by (block id i*G + g, local column).  It
-// runs as an LSD radix sort of 64-bit sort words
-//     block id << 32 | local column << 14 | local row
-// (the low 32 bits ARE the entry's packed key) that carry the entry's CSR
-// position, over the digits of (block id, local column) only:
-//   k_xsd_keys     a wave per 64 rows: every entry's sort word and position;
-//                  raises the `bad` flag (column outside [0, n), key overflow)
-//                  -- such an entry is only counted (word 0), its column never
-//                  becomes an address;
-//   per digit      k_xsd_count (tile histograms in LDS, stored plainly
-//                  [digit][tile]), scan_inclusive, k_xsd_scatter (stable
-//                  in-tile ranking by wave ballots, the tile staged in LDS in
-//                  digit order, written as per-digit runs).  No global atomic
-//                  decides a place, so the order is the same on every run;
-//   k_xsd_bounds   the blocks' entry offsets, read off the sorted words;
-//   k_xsd_chunks / scan / k_xsd_blk   blk[] in chunks (+ the bad flag), the
-//                  one array copied to the host -- the build's only wait;
-//   k_xsd_fill     a workgroup per chunk: gathers the values by position and
-//                  writes the chunk lane-transposed, padding included.
-// Any block size takes the same path (a block is just a run of the sorted
-// words).  Scratch: two (word, position) buffers of 12 B per entry plus the
-// digit counts, freed before returning.
-constexpr int kXdThreads = 256;
-constexpr int kXdWaves = kXdThreads / 64;
-constexpr int kXdItems = 16;
-constexpr int kXdTile = kXdThreads * kXdItems;  // entries per radix tile
-constexpr int kXdMaxBits = 8;                   // digit bits: one digit per thread
-static_assert(kXdThreads == 1 << kXdMaxBits, "one digit per thread");
-typedef unsigned long long xsw_t;
-
-struct XsDevRange {
-    int row0;
-    int lim;  // rows the range's keys may address
-};
-
-// the sorted part of a word: block id above the local column's cpb bits
-__device__ __forceinline__ unsigned long long xsd_sortbits(xsw_t w, int cpb)
-{
-    return ((w >> 32) << cpb) | ((w >> kXsRowBits) & ((1u << kXsColBits) - 1));
-}
-
-__device__ __forceinline__ int xsd_wave_incl_scan(int v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(v, off, 64);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
-__global__ __launch_bounds__(256) void k_xsd_keys(const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                  int m, int n, const XsDevRange *__restrict__ rng, int I,
-                                                  int G, int Wg, xsw_t *__restrict__ words,
-                                                  int *__restrict__ pos, int *__restrict__ bad)
-{
-    const int lane = threadIdx.x & 63;
-    const int r0 = ((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 64;
-    if (r0 >= m) return;
-    const int nrow = min(64, m - r0);
-    const int b = rowptr[min(r0 + lane, m)];
-    const int last = rowptr[r0 + nrow];
-    // this lane's row's range: the largest i with rng[i].row0 <= row
-    const int myrow = min(r0 + lane, m - 1);
-    int lo = 0, hi = I - 1;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo + 1) / 2;
-        if (rng[mid].row0 <= myrow) lo = mid;
-        else hi = mid - 1;
-    }
-    const XsDevRange mine = rng[lo];
-    for (int j = 0; j < nrow; ++j) {
-        const int s = __builtin_amdgcn_readlane(b, j);
-        const int e = j + 1 < nrow ? __builtin_amdgcn_readlane(b, j + 1) : last;
-        const int i = __builtin_amdgcn_readlane(lo, j);
-        const int row0 = __builtin_amdgcn_readlane(mine.row0, j);
-        const int lim = __builtin_amdgcn_readlane(mine.lim, j);
-        const unsigned lr = (unsigned)(r0 + j - row0);
-        for (int k = s + lane; k < e; k += 64) {
-            const int c = col[k];
-            xsw_t w = 0;
-            bool ok = c >= 0 && c < n;
-            if (ok) {
-                const int g = c / Wg;
-                const unsigned cp = (unsigned)(c - g * Wg);
-                ok = cp < (1u << kXsColBits) - 1 && lr < (unsigned)lim && g < G;
-                w = ((xsw_t)((unsigned)i * (unsigned)G + (unsigned)g) << 32) | ((xsw_t)cp << kXsRowBits) | lr;
-            }
-            if (!ok) {
-                w = 0;
-                *bad = 1;
-            }
-            words[k] = w;
-            pos[k] = k;
-        }
-    }
-}
-
-__global__ __launch_bounds__(kXdThreads) void k_xsd_count(const xsw_t *__restrict__ words, long long nnz,
-                                                          int shift, int rb, int cpb, int ntiles,
-                                                          int *__restrict__ counts)
-{
-    __shared__ int h[1 << kXdMaxBits];
-    const int t = threadIdx.x, dm = (1 << rb) - 1;
-    h[t] = 0;
-    __syncthreads();
-    const long long base = (long long)blockIdx.x * kXdTile;
-#pragma unroll
-    for (int j = 0; j < kXdItems; ++j) {
-        const long long i = base + j * kXdThreads + t;
-        if (i < nnz) atomicAdd(&h[(int)(xsd_sortbits(words[i], cpb) >> shift) & dm], 1);
-    }
-    __syncthreads();
-    if (t <= dm) counts[(size_t)t * ntiles + blockIdx.x] = h[t];
-}
-
-// One tile per workgroup.  Wave w ranks the contiguous quarter [w*1024,
-// (w+1)*1024) of the tile in 16 batches of 64 with wave-private digit
-// counters (a wave's LDS operations retire in program order): rank = the
-// wave's count so far + the in-batch rank from rb ballots.  The per-wave
-// counts then become the tile's digit offsets, the tile is staged in LDS in
-// digit order (stable: wave order, then batch order, then lane order = tile
-// order) and written out as per-digit runs from incl[] (the inclusive scan
-// of the [digit][tile] counts).
-__global__ __launch_bounds__(kXdThreads) void k_xsd_scatter(const xsw_t *__restrict__ win,
-                                                            const int *__restrict__ pin, long long nnz,
-                                                            int shift, int rb, int cpb, int ntiles,
-                                                            const int *__restrict__ incl,
-                                                            xsw_t *__restrict__ wout, int *__restrict__ pout)
-{
-    __shared__ int wcnt[kXdWaves][1 << kXdMaxBits];
-    __shared__ int lstart[1 << kXdMaxBits], gbase[1 << kXdMaxBits], wtot[kXdWaves];
-    __shared__ xsw_t sword[kXdTile];
-    __shared__ int spos[kXdTile];
-    constexpr int kQ = kXdTile / kXdWaves;
-    const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-    const int D = 1 << rb, dm = D - 1;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll
-    for (int q = 0; q < kXdWaves; ++q) wcnt[q][t] = 0;
-    const long long base = (long long)blockIdx.x * kXdTile;
-    const int valid = (int)min((long long)kXdTile, nnz - base);
-    xsw_t ww[kXdItems];
-    int pp[kXdItems], lp[kXdItems], dd[kXdItems];
-#pragma unroll
-    for (int j = 0; j < kXdItems; ++j) {
-        const int li = w * kQ + j * 64 + lane;
-        const bool ok = li < valid;
-        ww[j] = ok ? win[base + li] : 0;
-        pp[j] = ok ? pin[base + li] : 0;
-        dd[j] = (int)(xsd_sortbits(ww[j], cpb) >> shift) & dm;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kXdItems; ++j) {
-        const bool ok = w * kQ + j * 64 + lane < valid;
-        const int d = dd[j];
-        unsigned long long mm = __ballot(ok);
-        for (int b = 0; b < rb; ++b) {
-            const unsigned long long bal = __ballot((d >> b) & 1);
-            mm &= ((d >> b) & 1) ? bal : ~bal;
-        }
-        const int rank = __popcll(mm & lt);
-        const int sofar = wcnt[w][d];
-        lp[j] = sofar + rank;
-        if (ok && rank == 0) wcnt[w][d] = sofar + __popcll(mm);
-    }
-    __syncthreads();
-    // digit t: the waves' starts inside the digit, then the tile's digit offsets
-    int c = 0;
-    if (t < D) {
-#pragma unroll
-        for (int q = 0; q < kXdWaves; ++q) {
-            const int v = wcnt[q][t];
-            wcnt[q][t] = c;
-            c += v;
-        }
-    }
-    const int inc = xsd_wave_incl_scan(c);
-    if (lane == 63) wtot[w] = inc;
-    __syncthreads();
-    int ex = inc - c;
-    for (int q = 0; q < w; ++q) ex += wtot[q];
-    lstart[t] = ex;
-    gbase[t] = t < D ? incl[(size_t)t * ntiles + blockIdx.x] - c : 0;  // inclusive scan -> this tile's start
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kXdItems; ++j) {
-        if (w * kQ + j * 64 + lane < valid) {
-            const int p = lstart[dd[j]] + wcnt[w][dd[j]] + lp[j];
-            sword[p] = ww[j];
-            spos[p] = pp[j];
-        }
-    }
-    __syncthreads();
-    for (int li = t; li < valid; li += kXdThreads) {
-        const xsw_t k = sword[li];
-        const int d = (int)(xsd_sortbits(k, cpb) >> shift) & dm;
-        const long long g = (long long)gbase[d] + (li - lstart[d]);
-        if (g >= 0 && g < nnz) {  // always: the counts are this pass's own
-            wout[g] = k;
-            pout[g] = spos[li];
-        }
-    }
-}
-
-// start[k] = first sorted entry of block k (start[nblk] = nnz): the entry that
-// opens a new block id writes the starts of every block since the last one.
-__global__ __launch_bounds__(256) void k_xsd_bounds(const xsw_t *__restrict__ words, long long nnz,
-                                                    long long nblk, int *__restrict__ start)
-{
-    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= nnz) return;
-    const long long b = min((long long)(words[p] >> 32), nblk - 1);
-    const long long pb = p ? min((long long)(words[p - 1] >> 32), nblk - 1) : -1;
-    for (long long k = pb + 1; k <= b; ++k) start[k] = (int)p;
-    if (p == nnz - 1)
-        for (long long k = b + 1; k <= nblk; ++k) start[k] = (int)nnz;
-}
-
-__global__ __launch_bounds__(256) void k_xsd_chunks(const int *__restrict__ start, long long nblk,
-                                                    int *__restrict__ cnt)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k < nblk) cnt[k] = (start[k + 1] - start[k] + kXsChunk - 1) / kXsChunk;
-}
-
-// blk[0] = 0, blk[k + 1] = chunks of blocks 0..k, blk[nblk + 1] = the bad flag
-__global__ __launch_bounds__(256) void k_xsd_blk(const int *__restrict__ incl, long long nblk,
-                                                 const int *__restrict__ bad, long long *__restrict__ blk)
-{
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k < nblk) blk[k + 1] = incl[k];
-    if (k == 0) {
-        blk[0] = 0;
-        blk[nblk + 1] = *bad;
-    }
-}
-
-// One chunk per workgroup: thread p takes the chunk's entry p (a padding
-// entry past the block's end), the chunk is transposed through LDS and stored
-// whole: keys at 4*l + j, values at (j < 2 ? 0 : 128) + 2*l + (j & 1) for
-// l = p & 63, j = p >> 6.
-__global__ __launch_bounds__(kXsChunk) void k_xsd_fill(const xsw_t *__restrict__ words,
-                                                       const int *__restrict__ pos,
-                                                       const double *__restrict__ val, long long nnz,
-                                                       const int *__restrict__ start,
-                                                       const long long *__restrict__ blk, long long nblk,
-                                                       unsigned char *__restrict__ out)
-{
-    __shared__ uint32_t sk[kXsChunk];
-    __shared__ double sv[kXsChunk];
-    const long long c = blockIdx.x;
-    // the chunk's block: blk[k] <= c < blk[k + 1] (blk[0] = 0, blk[nblk] > c)
-    long long lo = 1, hi = nblk;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (blk[mid] > c) hi = mid;
-        else lo = mid + 1;
-    }
-    const long long k = lo - 1;
-    const int p = threadIdx.x;
-    const long long src = (long long)start[k] + (c - blk[k]) * kXsChunk + p;
-    const bool in = src >= 0 && src < (long long)start[k + 1] && src < nnz;
-    uint32_t key = kXsPad;
-    double v = 0.0;
-    if (in) {
-        key = (uint32_t)words[src];
-        const int e = pos[src];
-        v = (e >= 0 && e < nnz) ? val[e] : 0.0;  // always in range: a permutation of the positions
-    }
-    const int l = p & 63, j = p >> 6;
-    sk[4 * l + j] = key;
-    sv[(j < 2 ? 0 : 128) + 2 * l + (j & 1)] = v;
-    __syncthreads();
-    unsigned char *oc = out + (size_t)c * kXsChunkBytes;
-    reinterpret_cast<uint32_t *>(oc)[p] = sk[p];
-    reinterpret_cast<double *>(oc + kXsChunk * sizeof(uint32_t))[p] = sv[p];
-}
-
-namespace {
-// the device build's temporaries: freed together, whatever way it returns
-struct XsScratch {
-    std::vector<void *> ptrs;
-    long long bytes = 0;
-    bool deny = false;  // test hook "xs_devplan_nomem": the second allocation fails
-    template <class T>
-    bool take(T **p, size_t count)
-    {
-        const size_t b = sizeof(T) * std::max<size_t>(count, 1);
-        *p = nullptr;
-        if ((deny && !ptrs.empty()) || hipMalloc((void **)p, b) != hipSuccess) {
-            (void)hipGetLastError();  // not an error of the call: the host build takes over
-            *p = nullptr;
-            return false;
-        }
-        ptrs.push_back(*p);
-        bytes += (long long)b;
-        return true;
-    }
-    ~XsScratch()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-};
-
-size_t scan_scratch_len(long long len)
-{
-    size_t tot = 0;
-    for (long long t = len; t > 1;) {
-        t = (t + 2047) / 2048;  // scan_inclusive's tiles per level
-        tot += (size_t)t;
-    }
-    return tot + 2;
-}
-}  // namespace
-
-// on_device = false on return: nothing was published, build on the host
-static int xs_layout_device(sblas_csr_s &A, const std::vector<XsRange> &ranges, int rows_cap, int nrows_cap,
-                            hipStream_t s, std::vector<long long> &blk, bool &on_device)
-{
-    XsPlan &P = A.xs;
-    const int m = A.m, I = (int)ranges.size(), G = P.G, Wg = P.Wg;
-    const long long nnz = A.nnz;
-    const long long nblk = (long long)I * G;
-    on_device = true;
-    if (nnz == 0 || nblk == 0) {  // no entries: no chunks (the storage's one spare chunk is never read)
-        blk.assign((size_t)nblk + 1, 0);
-        SBLAS_HIP(hipMalloc(&P.key, kXsChunkBytes));
-        return SBLAS_OK;
-    }
-    if (nblk >= (1LL << 27)) {  // counts and offsets are scanned as 32-bit words
-        on_device = false;
-        return SBLAS_OK;
-    }
-    auto bits = [](long long v) {
-        int b = 0;
-        while (v > 0) {
-            ++b;
-            v >>= 1;
-        }
-        return b;
-    };
-    const int cpb = bits((long long)Wg - 1);  // local column < Wg
-    const int tot = cpb + bits(nblk - 1);
-    const int passes = (tot + kXdMaxBits - 1) / kXdMaxBits;
-    const int rb = passes ? (tot + passes - 1) / passes : 1;
-    const int ntiles = (int)((nnz + kXdTile - 1) / kXdTile);
-    const long long ncnt = (long long)ntiles << rb;
-
-    double opt = 0.0;
-    XsScratch sc;
-    sc.deny = test_option("xs_devplan_nomem", &opt) && opt != 0.0;
-    xsw_t *w0 = nullptr, *w1 = nullptr;
-    int *p0 = nullptr, *p1 = nullptr, *counts = nullptr, *cscr = nullptr, *start = nullptr, *cnt = nullptr,
-        *bscr = nullptr, *bad = nullptr;
-    long long *dblk = nullptr;
-    XsDevRange *drng = nullptr;
-    if (!sc.take(&w0, (size_t)nnz) || !sc.take(&p0, (size_t)nnz) || !sc.take(&w1, (size_t)nnz) ||
-        !sc.take(&p1, (size_t)nnz) || !sc.take(&counts, (size_t)ncnt) ||
-        !sc.take(&cscr, scan_scratch_len(ncnt)) || !sc.take(&start, (size_t)nblk + 1) ||
-        !sc.take(&cnt, (size_t)nblk) || !sc.take(&bscr, scan_scratch_len(nblk)) || !sc.take(&bad, 1) ||
-        !sc.take(&dblk, (size_t)nblk + 2) || !sc.take(&drng, (size_t)I)) {
-        on_device = false;
-        return SBLAS_OK;
-    }
-    std::vector<XsDevRange> hr((size_t)I);
-    for (int i = 0; i < I; ++i) hr[(size_t)i] = {ranges[(size_t)i].row0, ranges[(size_t)i].wide ? rows_cap : nrows_cap};
-    SBLAS_HIP(hipMemcpyAsync(drng, hr.data(), sizeof(XsDevRange) * (size_t)I, hipMemcpyHostToDevice, s));
-    SBLAS_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-    hipLaunchKernelGGL(k_xsd_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, A.rowptr, A.col, m, A.n,
-                       drng, I, G, Wg, w0, p0, bad);
-    for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(k_xsd_count, dim3((unsigned)ntiles), dim3(kXdThreads), 0, s, w0, nnz, p * rb, rb, cpb,
-                           ntiles, counts);
-        SBLAS_TRY(scan_inclusive(counts, ncnt, cscr, s));
-        hipLaunchKernelGGL(k_xsd_scatter, dim3((unsigned)ntiles), dim3(kXdThreads), 0, s, w0, p0, nnz, p * rb, rb,
-                           cpb, ntiles, counts, w1, p1);
-        std::swap(w0, w1);
-        std::swap(p0, p1);
-    }
-    hipLaunchKernelGGL(k_xsd_bounds, dim3((unsigned)((nnz + 255) / 256)), dim3(256), 0, s, w0, nnz, nblk, start);
-    const unsigned bgrid = (unsigned)((nblk + 255) / 256);
-    hipLaunchKernelGGL(k_xsd_chunks, dim3(bgrid), dim3(256), 0, s, start, nblk, cnt);
-    SBLAS_TRY(scan_inclusive(cnt, nblk, bscr, s));
-    hipLaunchKernelGGL(k_xsd_blk, dim3(bgrid), dim3(256), 0, s, cnt, nblk, bad, dblk);
-    SBLAS_HIP(hipGetLastError());
-    // the one wait of the build: blk[] (and the bad flag behind it)
-    std::vector<long long> hb((size_t)nblk + 2);
-    SBLAS_HIP(hipMemcpyAsync(hb.data(), dblk, sizeof(long long) * hb.size(), hipMemcpyDeviceToHost, s));
-    SBLAS_HIP(hipStreamSynchronize(s));
-    P.d2h_bytes += (long long)(sizeof(long long) * hb.size());
-    P.scratch_bytes = sc.bytes;
-    if (hb[(size_t)nblk + 1] != 0) {
-        set_error("%s", kXsBadMsg);
-        return SBLAS_ERR_INVALID;
-    }
-    hb.pop_back();
-    const long long nchunks = hb.back();
-    bool sane = hb[0] == 0 && nchunks >= 0 && nchunks <= nnz / kXsChunk + nblk;
-    for (size_t k = 0; sane && k < (size_t)nblk; ++k) sane = hb[k + 1] >= hb[k];
-    if (!sane) {
-        set_error("xsort: device layout build produced inconsistent block offsets");
-        return SBLAS_ERR_HIP;
-    }
-    if (hipMalloc(&P.key, (size_t)std::max<long long>(nchunks, 1) * kXsChunkBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        P.key = nullptr;
-        on_device = false;  // the host build holds no scratch beside the storage
-        return SBLAS_OK;
-    }
-    if (nchunks)
-        hipLaunchKernelGGL(k_xsd_fill, dim3((unsigned)nchunks), dim3(kXsChunk), 0, s, w0, p0, A.val, nnz, start,
-                           dblk, nblk, reinterpret_cast<unsigned char *>(P.key));
-    SBLAS_HIP(hipGetLastError());
-    // the scratch is freed on return: the fill must have read it
-    SBLAS_HIP(hipStreamSynchronize(s));
-    blk.swap(hb);
-    return SBLAS_OK;
-}
-
+// The plan build: what to run is decided by the planner (xs_plan_host in
+// xsort_plan.cpp: pure host arithmetic), the chunk storage comes from a
+// layout builder (xsort_layout.hip); the item records, the uploads and the
+// plan's statistics are made here.
 int build_xsort_plan(sblas_csr_s &A, hipStream_t s)
 {
     if (A.xs.ready) return SBLAS_OK;
     const auto t_entry = std::chrono::steady_clock::now();
     DeviceGuard dg(A.device);
     XsPlan &P = A.xs;
-    const int m = A.m, n = A.n;
-    const long long nnz = A.nnz;
-    const std::vector<int> &rp = A.h_rowptr;
-    double opt = 0.0;
 
-    // column groups: G = 8q groups of Wg < 2^18 columns (the all-ones column
-    // field is the padding key) and ~1 MiB of x (an XCD's current group plus
-    // the entry stream must fit its 4 MiB L2)
-    const long long wmax = (1LL << kXsColBits) - 1;
-    const long long ng = ((long long)std::max(n, 1) + wmax - 1) / wmax;
-    const long long nmib = ((long long)std::max(n, 1) * 8 + (1LL << 20) - 1) >> 20;
-    P.q = (int)std::max<long long>({1LL, (ng + 7) / 8, (nmib + 7) / 8});
-    P.G = 8 * P.q;
-    if (P.G > 127) {
-        set_error("xsort: n = %d needs %d column groups (> 127)", n, P.G);
-        return SBLAS_ERR_UNSUPPORTED;
-    }
-    P.Wg = (int)std::max<long long>(1, ((long long)std::max(n, 1) + P.G - 1) / P.G);
-    const int G = P.G, Wg = P.Wg;
-
-    // Workgroup: two 4-wave teams (512 threads, 2 waves per SIMD, up to 256
-    // VGPRs a wave) -- the register budget lets the compiler keep more of the
-    // stream in flight than two 8-wave teams (1024 threads, 128 VGPRs) or two
-    // 6-wave teams (768, ~170): config 2 N = 1 / 2 / 4 / 8 150.6-152.5 /
-    // 96.4-96.7 / 65.5-65.6 / 40.7-40.8 us against 153.0-153.3 / 99.1 /
-    // 66.3-66.9 / 42.1-42.5, 27-point 128^3 117 vs 121, 7-point 160^3 83 vs
-    // 85, R-MAT equal (profiles/r05/wg512p/).  Resident workgroups = item
-    // slots; a paired item holds two sub-items.
+    // resident workgroups = item slots (one per CU: the LDS rows)
     int dev = 0, ncu = 0, per_cu = 0;
     SBLAS_HIP(hipGetDevice(&dev));
     SBLAS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
     SBLAS_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_spmv_xsort<true>, kXsThreads, 0));
     const int resident = std::max(1, ncu * std::max(per_cu, 1));
-    const long long slots = (long long)resident * 2;  // sub-items
-    // every range wide (8 XCD-local sub-items + partials per row) on small
-    // matrices: a rank's slice of the uniform config 2 at N = 8 (5.0M
-    // entries) 47.0 -> 41.8 us, N = 16 (2.5M) 33.8 -> 29.9, but N = 4 (9.9M)
-    // 66.8 -> 104 (profiles/r05/sweep2/): the partials (16 B per row and XCD)
-    // outweigh XCD-local gathers beyond ~6M entries.
-    const bool all_wide = test_option("xs_allwide", &opt) ? opt != 0.0 : nnz <= kXsAllWideMaxNnz;
-    const int rows_cap = kXsHalfRows;
-    // Solo narrow items: a narrow range is an item of its own -- both teams'
-    // waves and all 16,384 LDS rows -- so its blocks are twice as dense
-    // (fewer x line requests per entry); wide ranges still pair (wide, wide)
-    // at 8,192 rows a team.  Chosen when >= 40% of the rows are empty
-    // (power-law graphs: an empty row spends an accumulator row, so 16,384
-    // rows per light range hold what 8,192 would without them): R-MAT scale
-    // 21 (50% empty) 158.8 -> 147.3 us; config 2 and the stencils have none
-    // and keep pairs (solo there: 146.7 vs 131 us; profiles/r04/rmat/).
-    {
-        long long empty = 0;
-        for (int r = 0; r < m; ++r) empty += rp[r + 1] == rp[r];
-        P.solo = test_option("xs_solo", &opt) ? opt != 0.0 : (m > 0 && 5 * empty >= 2LL * m);
-    }
-    const int nrows_cap = P.solo ? kXsItemRows : rows_cap;  // narrow ranges
-    const double nfac = P.solo ? 2.0 : 1.0;                 // a narrow range's cost, in sub-item caps
+    double opt = 0.0;
+    XsPlanOptions po;
+    if (test_option("xs_allwide", &opt)) po.allwide = opt != 0.0;
+    if (test_option("xs_solo", &opt)) po.solo = opt != 0.0;
+    po.has_cap = test_option("xs_cap", &po.cap);
+    bool on_device = !(test_option("xs_hostplan", &opt) && opt != 0.0);
 
-    // Cost model (work units ~ one streamed entry): a sub-item's time is its
-    // entries plus lambda per distinct x line its gathers touch; with uniform
-    // columns a block of c entries over L lines touches L*(1 - exp(-c/L))
-    // lines.  A narrow sub-item spreads its entries over all of x (G*Lg
-    // lines), a wide one its 1/8 share over its XCD's q groups.  lambda = 1.0
-    // is the best of a sweep (0.3 .. 1.7) on config 2.
-    const double lam = 1.0;
-    const double Lg = std::max(1.0, Wg / 16.0);  // 128-B lines of one group's x slice
-    auto narrow_cost = [&](double c) { return c + lam * G * Lg * (1.0 - std::exp(-c / (G * Lg))); };
-    auto wide_cost = [&](double c) {
-        const double ci = c / 8.0;
-        return ci + lam * P.q * Lg * (1.0 - std::exp(-ci / (P.q * Lg)));
-    };
-    // Row ranges: from row r, a wide candidate takes <= rows_cap rows while
-    // one of its 8 sub-items costs <= cap.  It is WIDE (8 sub-items + 8
-    // partials per row) when it holds more than one narrow sub-item's work and
-    // its rows average >= 16 entries (the partials then cost <= 8 B per
-    // entry); otherwise a narrow range of cost <= cap is cut afresh from r.
-    std::vector<XsRange> ranges;
-    auto build_ranges = [&](double cap) {
-        ranges.clear();
-        // cut(r): the first row always, then rows while the range's cost stays
-        // <= cap, at most rows_cap rows.  The cost grows strictly with the
-        // entry count rp[e] - rp[r], so the end is a binary search over e
-        // (O(log m) cost evaluations per range instead of one per row: the
-        // cap search below runs build_ranges many times over all m rows).
-        auto cut = [&](int r, bool wide, long long &cnt) {
-            const int start = r;
-            const int emax = (int)std::min<long long>(m, (long long)start + (wide ? rows_cap : nrows_cap));
-            auto fits = [&](int e) {
-                const double c = (double)(rp[e] - rp[start]);
-                return wide ? wide_cost(c) <= cap : narrow_cost(c) <= nfac * cap;
-            };
-            int lo = start + 1, hi = emax;  // answer in [lo, hi]; lo always taken
-            while (lo < hi) {
-                const int mid = lo + (hi - lo + 1) / 2;
-                if (fits(mid)) lo = mid;
-                else hi = mid - 1;
-            }
-            cnt = rp[lo] - rp[start];
-            return lo;
-        };
-        int r = 0;
-        while (r < m) {
-            long long cnt;
-            int e = cut(r, true, cnt);
-            const bool wide = cnt > 0 && (all_wide || (narrow_cost((double)cnt) > nfac * cap &&
-                                                      cnt >= 16LL * (e - r)));
-            if (!wide) e = cut(r, false, cnt);
-            XsRange R{};
-            R.row0 = r;
-            R.nrows = e - r;
-            R.wide = wide ? 1 : 0;
-            ranges.push_back(R);
-            r = e;
-        }
-    };
-    auto count_subs = [&]() {
-        long long c = 0;
-        for (const XsRange &R : ranges) c += R.wide ? 8 : P.solo ? 2 : 1;
-        return c;
-    };
-    // grow the sub-item cost until the sub-items fit the resident grid (a
-    // second round for a few items would double the kernel's tail).  The
-    // "xs_cap" test hook fixes the cap instead (many small items: the
-    // dynamic claims run on small matrices).
-    const bool fixed_cap = test_option("xs_cap", &opt);
-    double cap = fixed_cap ? std::max(1.0, opt) : narrow_cost((double)nnz) / (double)slots;
-    // Ranges hold at most rows_cap rows, so once ceil(m / rows_cap) exceeds
-    // the slots no cap can fit them: stop there (and after 50 growth steps
-    // without fewer sub-items) instead of 400 O(m) passes.  Leftover
-    // sub-items are still correct: the grid claims them in a second round.
-    const long long min_ranges = ((long long)m + rows_cap - 1) / rows_cap;
-    long long best_subs = -1;
-    for (int it = 0, flat = 0; it < 400; ++it) {
-        build_ranges(cap);
-        const long long subs = count_subs();
-        if (subs <= slots || fixed_cap || min_ranges > slots) break;
-        flat = (best_subs >= 0 && subs >= best_subs) ? flat + 1 : 0;
-        if (flat >= 50) break;
-        if (best_subs < 0 || subs < best_subs) best_subs = subs;
-        cap *= 1.02;
-    }
-    const int I = (int)ranges.size();
-    if ((long long)I >= (1LL << 23)) {
-        set_error("xsort: %d row ranges (> 2^23)", I);
-        return SBLAS_ERR_UNSUPPORTED;
-    }
+    XsHostPlan H;
+    SBLAS_TRY(xs_plan_host(A.m, A.n, A.nnz, A.h_rowptr.data(), resident, po, H));
+    const std::vector<XsRange> &ranges = H.ranges;
+    const int G = H.G;
+    P.q = H.q;
+    P.G = H.G;
+    P.Wg = H.Wg;
+    P.solo = H.solo;
 
     // The layout: every block (range, group) sorted by (column, row), padded
     // to whole chunks, every chunk stored lane-transposed (header comment):
@@ -1131,105 +477,16 @@ int build_xsort_plan(sblas_csr_s &A, hipStream_t s)
     // the host build (xs_layout_host; test hook "xs_hostplan") gives the same
     // bytes and is the fallback when the device build's scratch does not fit.
     const size_t cbytes = kXsChunkBytes;
-    P.kstride = (int)(cbytes / 16);
-    P.vstride = (int)(cbytes / 16);
-    P.dev_built = false;
-    P.scratch_bytes = 0;
-    P.d2h_bytes = 0;
+    P.kstride = P.vstride = (int)(cbytes / 16);
+    P.scratch_bytes = P.d2h_bytes = 0;
     std::vector<long long> blk;  // chunk offsets
     std::unique_ptr<unsigned char[]> hbuf;
-    bool on_device = !(test_option("xs_hostplan", &opt) && opt != 0.0);
-    if (on_device) SBLAS_TRY(xs_layout_device(A, ranges, rows_cap, nrows_cap, s, blk, on_device));
-    if (!on_device) SBLAS_TRY(xs_layout_host(A, ranges, rows_cap, nrows_cap, blk, hbuf));
+    if (on_device) SBLAS_TRY(xs_layout_device(A, ranges, H.rows_cap, H.nrows_cap, s, blk, on_device));
+    if (!on_device) SBLAS_TRY(xs_layout_host(A, ranges, H.rows_cap, H.nrows_cap, blk, hbuf));
     P.dev_built = on_device;
     const long long nchunks = blk.back();
     const size_t hb_n = (size_t)std::max<long long>(nchunks, 1) * cbytes;
 
-    // sub-items, wide partial slots, then items (pairs) in XCD queues
-    std::vector<int> wide, nsub;
-    std::vector<std::vector<int>> wsub(8);
-    long long pbase = 0;
-    for (int i = 0; i < I; ++i) {
-        XsRange &R = ranges[i];
-        R.widx = -1;
-        if (R.wide) {
-            R.pbase = pbase;
-            pbase += 8LL * R.nrows;
-            R.widx = (int)wide.size();
-            wide.push_back(i);
-            for (int k = 0; k < 8; ++k) wsub[k].push_back((i << 8) | (k + 1));
-        } else {
-            nsub.push_back(i << 8);
-        }
-    }
-    std::vector<std::vector<std::pair<int, int>>> q(8);
-    if (P.solo) {
-        // solo narrow items (narrow, -1); wide sub-items paired within their
-        // XCD; each queue alternates the two kinds
-        std::vector<std::vector<std::pair<int, int>>> qn(8), qw(8);
-        for (size_t j = 0; j < nsub.size(); ++j) qn[j % 8].push_back({nsub[j], -1});
-        for (int k = 0; k < 8; ++k)
-            for (size_t j = 0; j < wsub[k].size(); j += 2)
-                qw[k].push_back({wsub[k][j], j + 1 < wsub[k].size() ? wsub[k][j + 1] : -1});
-        for (int k = 0; k < 8; ++k)
-            for (size_t j = 0; j < std::max(qn[k].size(), qw[k].size()); ++j) {
-                if (j < qn[k].size()) q[k].push_back(qn[k][j]);
-                if (j < qw[k].size()) q[k].push_back(qw[k][j]);
-            }
-    } else {
-        // a narrow (gather-bound) with a wide (stream-bound) sub-item where
-        // possible, the XCDs interleaved so the narrow ones spread evenly;
-        // leftovers pair among themselves (wide ones within their XCD)
-        size_t ni = 0;
-        std::vector<std::vector<int>> wleft(8);
-        for (size_t j = 0;; ++j) {
-            bool any = false;
-            for (int k = 0; k < 8; ++k) {
-                if (j >= wsub[k].size()) continue;
-                any = true;
-                if (ni < nsub.size()) q[k].push_back({nsub[ni++], wsub[k][j]});
-                else wleft[k].push_back(wsub[k][j]);
-            }
-            if (!any) break;
-        }
-        for (int k = 0; k < 8; ++k)
-            for (size_t j = 0; j < wleft[k].size(); j += 2)
-                q[k].push_back({wleft[k][j], j + 1 < wleft[k].size() ? wleft[k][j + 1] : -1});
-        // leftover light sub-items: two to an item only as far as the grid
-        // needs it; the rest run alone (both teams on one sub-item), so an
-        // item never carries twice a light sub-item's work while workgroups
-        // idle (power-law matrices: most rows light, few heavy sub-items)
-        long long items_now = 0;
-        for (int k = 0; k < 8; ++k) items_now += (long long)q[k].size();
-        const long long left = (long long)(nsub.size() - ni);
-        const long long free_slots = std::max<long long>(0, (long long)resident - items_now);
-        long long npairs = std::max<long long>(0, left - free_slots);  // items = left - npairs <= free
-        if (2 * npairs > left) npairs = left / 2;
-        for (int t = 0; ni < nsub.size(); ++t) {
-            const int a0 = nsub[ni++];
-            const int a1 = (npairs > 0 && ni < nsub.size()) ? nsub[ni++] : -1;
-            if (a1 >= 0) --npairs;
-            q[t % 8].push_back({a0, a1});
-        }
-    }
-    P.nranges = I;
-    P.nwide = (int)wide.size();
-    P.nchunks = nchunks;
-    P.qstride = 1;
-    P.nitems = 0;
-    for (int k = 0; k < 8; ++k) {
-        P.qlen[k] = (int)q[k].size();
-        P.qstride = std::max(P.qstride, P.qlen[k]);
-        P.nitems += P.qlen[k];
-    }
-    P.grid = std::min(P.nitems, resident);
-    int nstat = 0;
-    for (int k = 0; k < 8; ++k) {
-        const int blocks_k = P.grid > k ? (P.grid - k + 7) / 8 : 0;  // blocks b < grid with b % 8 == k
-        P.qstat[k] = std::min(P.qlen[k], blocks_k);
-        nstat += P.qstat[k];
-    }
-    P.dynamic = nstat < P.nitems ? 1 : 0;
     {  // most chunks of one item (both sub-items), for the plan's statistics
         auto nch = [&](int sub) -> long long {
             if (sub < 0) return 0;
@@ -1239,57 +496,65 @@ int build_xsort_plan(sblas_csr_s &A, hipStream_t s)
         };
         long long mc = 0;
         for (int k = 0; k < 8; ++k)
-            for (const auto &it : q[k]) mc = std::max(mc, nch(it.first) + nch(it.second));
+            for (const auto &it : H.queue[k]) mc = std::max(mc, nch(it.first) + nch(it.second));
         P.maxc = (int)std::min<long long>(mc, 1 << 30);
     }
-    std::vector<int> qflat((size_t)16 * P.qstride, -1);
-    for (int k = 0; k < 8; ++k)
-        for (size_t j = 0; j < q[k].size(); ++j) {
-            qflat[2 * ((size_t)k * P.qstride + j)] = q[k][j].first;
-            qflat[2 * ((size_t)k * P.qstride + j) + 1] = q[k][j].second;
-        }
 
-    SBLAS_HIP(hipMalloc(&P.wranges, sizeof(XsRange) * std::max<size_t>(wide.size(), 1)));
+    const long long pbase = H.partial_len;
+    SBLAS_HIP(hipMalloc(&P.wranges, sizeof(XsRange) * std::max<size_t>(H.wide.size(), 1)));
     if (!on_device) SBLAS_HIP(hipMalloc(&P.key, hb_n));  // the device build filled its own
     P.val = (double *)((unsigned char *)P.key + kXsChunk * sizeof(uint32_t));
     SBLAS_HIP(hipMalloc(&P.qhead, sizeof(int) * 32));  // [2 parities][8 claim heads + pad]
     {
         std::vector<int> h(32, 0);
-        for (int k = 0; k < 8; ++k) h[k] = h[16 + k] = P.qstat[k];
+        for (int k = 0; k < 8; ++k) h[k] = h[16 + k] = H.qstat[k];
         SBLAS_HIP(hipMemcpy(P.qhead, h.data(), sizeof(int) * 32, hipMemcpyHostToDevice));
     }
     SBLAS_HIP(hipMalloc(&P.partial, sizeof(double) * std::max<long long>(pbase, 1)));
-    if (!wide.empty()) {
+    if (!H.wide.empty()) {
         std::vector<XsRange> wr;
-        for (int i : wide) wr.push_back(ranges[(size_t)i]);
+        for (int i : H.wide) wr.push_back(ranges[(size_t)i]);
         SBLAS_HIP(hipMemcpy(P.wranges, wr.data(), sizeof(XsRange) * wr.size(), hipMemcpyHostToDevice));
     }
     if (!on_device && nchunks) SBLAS_HIP(hipMemcpy(P.key, hbuf.get(), hb_n, hipMemcpyHostToDevice));
-    long long xrec_bytes = 0;
-    {
+    {  // the item records, one per (queue slot, team); -1 throughout: no sub-item
         const size_t rl = (size_t)G + 5;
-        std::vector<long long> xrec(qflat.size() * rl, -1);
-        for (size_t s2 = 0; s2 < qflat.size(); ++s2) {
-            const int sub = qflat[s2];
-            long long *r = xrec.data() + s2 * rl;
-            r[0] = sub;
-            if (sub < 0) continue;
+        std::vector<long long> xrec((size_t)16 * H.qstride * rl, -1);
+        auto record = [&](size_t slot, int sub) {
+            if (sub < 0) return;
+            long long *r = xrec.data() + slot * rl;
             const XsRange &R = ranges[(size_t)(sub >> 8)];
+            r[0] = sub;
             r[1] = (long long)(unsigned)R.row0 | ((long long)R.nrows << 32);
             r[2] = R.pbase;
             r[3] = R.widx;
             for (int g = 0; g <= G; ++g) r[4 + g] = blk[(size_t)(sub >> 8) * G + g];
-        }
+        };
+        for (int k = 0; k < 8; ++k)
+            for (size_t j = 0; j < H.queue[k].size(); ++j) {
+                record(2 * ((size_t)k * H.qstride + j), H.queue[k][j].first);
+                record(2 * ((size_t)k * H.qstride + j) + 1, H.queue[k][j].second);
+            }
         SBLAS_HIP(hipMalloc(&P.xrec, sizeof(long long) * xrec.size()));
         SBLAS_HIP(hipMemcpy(P.xrec, xrec.data(), sizeof(long long) * xrec.size(), hipMemcpyHostToDevice));
-        xrec_bytes = (long long)(sizeof(long long) * xrec.size());
+        P.xrec_bytes = (long long)(sizeof(long long) * xrec.size());
     }
-    P.xrec_bytes = xrec_bytes;
     // the plan's device bytes, the same sum whichever way the layout was built
     // (the device build's scratch is gone again)
-    A.plan_bytes[SBLAS_SPMV_XSORT] = (long long)(sizeof(XsRange) * std::max<size_t>(wide.size(), 1)) +
+    A.plan_bytes[SBLAS_SPMV_XSORT] = (long long)(sizeof(XsRange) * std::max<size_t>(H.wide.size(), 1)) +
                                      (long long)hb_n + (long long)sizeof(int) * 32 +
-                                     (long long)sizeof(double) * std::max<long long>(pbase, 1) + xrec_bytes;
+                                     (long long)sizeof(double) * std::max<long long>(pbase, 1) + P.xrec_bytes;
+    P.nranges = (int)ranges.size();
+    P.nwide = (int)H.wide.size();
+    P.nchunks = nchunks;
+    P.nitems = H.nitems;
+    P.grid = H.grid;
+    P.dynamic = H.dynamic;
+    P.qstride = H.qstride;
+    for (int k = 0; k < 8; ++k) {
+        P.qlen[k] = H.qlen[k];
+        P.qstat[k] = H.qstat[k];
+    }
     P.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_entry).count();
     P.ready = true;
     return SBLAS_OK;

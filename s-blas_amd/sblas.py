@@ -119,6 +119,7 @@ _sig("sblas_peer_refs", _i, _i, _i)
 _sig("sblas_test_set_option", _i, C.c_char_p, _d, _i)
 _sig("sblas_csr_set_deterministic", _i, _p, _i)
 _sig("sblas_csr_xsort_info", _i, _p, _p)
+_sig("sblas_xsort_plan_host", _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _ll, _p, _ll)
 _sig("sblas_csr_get_deterministic", _i, _p, _p)
 _sig("sblas_csr_xsort_export", _i, _p, _i, _p, _ll, _p)
 _sig("sblas_csr_xsort_build_info", _i, _p, _p)
@@ -230,6 +231,31 @@ def partition_cost(rowptr: np.ndarray, g: int, w: float = 3.0):
     check(lib.sblas_partition_cost(m, ptr(rp), g, float(w), ptr(si), ptr(ei), ptr(sr), ptr(er), ptr(sf)),
           "partition_cost")
     return si, ei, sr, er, sf
+
+
+def xsort_plan_host(rowptr, n: int, resident: int, cap=None, allwide=None, solo=None) -> dict:
+    """What the XSORT planner decides for a row structure (sblas_xsort_plan_host;
+    no GPU): the scalars q, G, Wg, solo, nranges, nwide, nitems, grid, dynamic,
+    qstride, partial_len; qlen / qstat [8]; ranges [nranges, 5] (row0, nrows,
+    wide, widx, pbase); queues: per XCD queue its items [len, 2] (sub0, sub1).
+    cap / allwide / solo override the planner as the test options do."""
+    rp = np.ascontiguousarray(rowptr, np.int64)
+    m = len(rp) - 1
+    c = None if cap is None else C.byref(C.c_double(cap))
+    aw = -1 if allwide is None else int(bool(allwide))
+    so = -1 if solo is None else int(bool(solo))
+    info = np.zeros(27, np.int64)
+    check(lib.sblas_xsort_plan_host(m, n, ptr(rp), resident, c, aw, so, ptr(info), None, 0, None, 0),
+          "xsort_plan_host")
+    ranges = np.zeros((int(info[4]), 5), np.int64)
+    items = np.zeros((int(info[6]), 2), np.int32)
+    check(lib.sblas_xsort_plan_host(m, n, ptr(rp), resident, c, aw, so, ptr(info), ptr(ranges), len(ranges),
+                                    ptr(items), len(items)), "xsort_plan_host")
+    keys = ("q", "G", "Wg", "solo", "nranges", "nwide", "nitems", "grid", "dynamic", "qstride", "partial_len")
+    out = {k: int(v) for k, v in zip(keys, info)}
+    out["qlen"], out["qstat"], out["ranges"] = info[11:19].copy(), info[19:27].copy(), ranges
+    out["queues"] = np.split(items, np.cumsum(out["qlen"])[:-1])
+    return out
 
 
 def coo_sortbyrow(m: int, row, col, val):
