@@ -252,10 +252,22 @@ int sblas_spmm(sblas_csr A, int n, double alpha, const double *d_B, int ldb,
 /* Device CSR -> CSC transpose of a handle; outputs DEVICE arrays sized
  * colptr[n+1], rowidx[nnz], cval[nnz]; row indices ascend within columns
  * (bit-exact with tranpose.h:6-43).  A stable sort of the entries by column:
- * MSD partition passes + one pass per final bucket of columns (n > 512), or
- * LSD radix passes (n <= 512, or SBLAS_TRANSPOSE_ALGO=lsd). */
+ * MSD partition passes + one pass per final bucket of columns (512 < n <=
+ * 2^24), or LSD radix passes (n <= 512 or n > 2^24). */
 int sblas_csr_transpose(sblas_csr A, int *d_colptr, int *d_rowidx,
                         double *d_cval, void *stream);
+/* What the transpose decides before its first launch for an m x n matrix of
+ * nnz entries on a device of ncu CUs, for inspection and tests; needs no GPU.
+ * info[18]: msd (1: MSD passes, 0: LSD), c, bA, bB (MSD digit bits: last
+ * pass, pass A, pass B), passes, rb (LSD passes and digit bits), ntiles
+ * (4096-entry tiles), S, nwg (tiles per workgroup and workgroups of pass A /
+ * the LSD passes), JB, nwgB (pass B: parts per pass-A bucket, workgroups),
+ * packA (key bits of the word pass A may hand pass B, -1: never), pack (key
+ * bits of the word pass B hands the last pass, -1: keys and rows apart), nbC
+ * (final buckets), ftile (last-pass tile, 3072 / 4096), lean (last pass
+ * without row staging), fgrid (its workgroups), ncnt (digit counts, ints).
+ * Fields of the form not taken are 0 (packA, pack: -1). */
+int sblas_transpose_shape_host(int m, int n, long long nnz, int ncu, long long *info);
 
 /* Triangular solve handle over a DEVICE lower/upper CSC matrix with the
  * diagonal stored first (lower) / last (upper) in each column. */

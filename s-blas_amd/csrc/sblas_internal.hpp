@@ -302,7 +302,6 @@ void free_plans(sblas_csr_s &A);
 int launch_spmv_panel(const sblas_csr_s &A, double alpha, const double *x,
                       double beta, double *y, hipStream_t s);
 int build_panel_plan(sblas_csr_s &A, hipStream_t s);
-int scan_inclusive(int *a, long long len, int *scratch, hipStream_t s);
 
 int launch_spmv_xsort(const sblas_csr_s &A, double alpha, const double *x,
                       double beta, double *y, hipStream_t s);

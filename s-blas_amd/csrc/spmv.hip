@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "sblas_internal.hpp"
+#include "scan.hpp"
 
 namespace sblas {
 
@@ -993,7 +994,7 @@ static int build_csr5_plan_device(Csr5Plan &P, const int *rowptr, int m, long lo
                        nnz, nt, P.flags, P.tile_row, P.seg_off + 1);
     SBLAS_HIP(hipGetLastError());
     int *scratch = nullptr;
-    SBLAS_HIP(hipMalloc(&scratch, sizeof(int) * (nt / 1024 + 256)));
+    SBLAS_HIP(hipMalloc(&scratch, sizeof(int) * scan_scratch_len(nt)));
     const int st = scan_inclusive(P.seg_off + 1, nt, scratch, s);
     int h[2] = {0, 0};
     if (st == SBLAS_OK) {
@@ -1461,7 +1462,7 @@ static int split_panels(const sblas_csr_s &A, int P, hipStream_t s, PanelCsr &o)
             hipLaunchKernelGGL(k_panel_count_long, dim3((unsigned)((nlong + 3) / 4)), dim3(256), 0, s, A.rowptr,
                                A.col, (int)m, o.W, P, dlong, nlong, o.rowptr);
         int *scratch = nullptr;
-        SBLAS_HIP(hipMalloc(&scratch, sizeof(int) * ((m + 1) / 1024 + 256)));
+        SBLAS_HIP(hipMalloc(&scratch, sizeof(int) * scan_scratch_len(m + 1)));
         for (int p = 0; p < P; ++p) SBLAS_TRY(scan_inclusive(o.rowptr + p * (m + 1), m + 1, scratch, s));
         SBLAS_HIP(hipStreamSynchronize(s));
         (void)hipFree(scratch);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sblas_internal.hpp"
+#include "scan.hpp"
 
 namespace sblas {
 
@@ -156,17 +157,6 @@ __device__ __forceinline__ unsigned long long xsd_sortbits(xsw_t w, int cpb)
     return ((w >> 32) << cpb) | ((w >> kXsRowBits) & ((1u << kXsColBits) - 1));
 }
 
-__device__ __forceinline__ int xsd_wave_incl_scan(int v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(v, off, 64);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_xsd_keys(const int *__restrict__ rowptr, const int *__restrict__ col,
                                                   int m, int n, const XsDevRange *__restrict__ rng, int I,
                                                   int G, int Wg, xsw_t *__restrict__ words,
@@ -294,7 +284,7 @@ __global__ __launch_bounds__(kXdThreads) void k_xsd_scatter(const xsw_t *__restr
             c += v;
         }
     }
-    const int inc = xsd_wave_incl_scan(c);
+    const int inc = wave_incl_scan(c);
     if (lane == 63) wtot[w] = inc;
     __syncthreads();
     int ex = inc - c;
@@ -422,15 +412,6 @@ struct XsScratch {
     }
 };
 
-size_t scan_scratch_len(long long len)
-{
-    size_t tot = 0;
-    for (long long t = len; t > 1;) {
-        t = (t + 2047) / 2048;  // scan_inclusive's tiles per level
-        tot += (size_t)t;
-    }
-    return tot + 2;
-}
 }  // namespace
 
 // on_device = false on return: nothing was published, build on the host

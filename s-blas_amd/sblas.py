@@ -120,6 +120,7 @@ _sig("sblas_test_set_option", _i, C.c_char_p, _d, _i)
 _sig("sblas_csr_set_deterministic", _i, _p, _i)
 _sig("sblas_csr_xsort_info", _i, _p, _p)
 _sig("sblas_xsort_plan_host", _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _ll, _p, _ll)
+_sig("sblas_transpose_shape_host", _i, _i, _i, _ll, _i, _p)
 _sig("sblas_csr_get_deterministic", _i, _p, _p)
 _sig("sblas_csr_xsort_export", _i, _p, _i, _p, _ll, _p)
 _sig("sblas_csr_xsort_build_info", _i, _p, _p)
@@ -256,6 +257,18 @@ def xsort_plan_host(rowptr, n: int, resident: int, cap=None, allwide=None, solo=
     out["qlen"], out["qstat"], out["ranges"] = info[11:19].copy(), info[19:27].copy(), ranges
     out["queues"] = np.split(items, np.cumsum(out["qlen"])[:-1])
     return out
+
+
+def transpose_shape_host(m: int, n: int, nnz: int, ncu: int) -> dict:
+    """What the transpose decides before its first launch for an m x n matrix
+    of nnz entries on ncu CUs (sblas_transpose_shape_host; no GPU): msd, c, bA,
+    bB, passes, rb, ntiles, S, nwg, JB, nwgB, packA, pack, nbC, ftile, lean,
+    fgrid, ncnt."""
+    info = np.zeros(18, np.int64)
+    check(lib.sblas_transpose_shape_host(m, n, nnz, ncu, ptr(info)), "transpose_shape_host")
+    keys = ("msd", "c", "bA", "bB", "passes", "rb", "ntiles", "S", "nwg", "JB", "nwgB", "packA", "pack", "nbC",
+            "ftile", "lean", "fgrid", "ncnt")
+    return {k: int(v) for k, v in zip(keys, info)}
 
 
 def coo_sortbyrow(m: int, row, col, val):

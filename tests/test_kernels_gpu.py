@@ -5,20 +5,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from transpose_cases import CASES, EDGES, MGPU_CASES, rand_csr, transpose_case, transpose_edge
 
 pytestmark = pytest.mark.gpu
-
-
-def rand_csr(rng, m, n, maxlen, empty_frac=0.1, long_rows=()):
-    lens = rng.integers(0, maxlen, m)
-    lens[rng.random(m) < empty_frac] = 0
-    for r, L in long_rows:
-        lens[r] = L
-    lens = np.minimum(lens, n)
-    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    col = (np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens]).astype(np.int32)
-           if rp[-1] else np.zeros(0, np.int32))
-    return rp, col, rng.standard_normal(int(rp[-1]))
 
 
 # ---------------------------------------------------------------- SpMM ----
@@ -132,50 +121,25 @@ def test_csrmm_reference_api(torch_cuda, sb, orc, ngpu, split):
 
 
 # ----------------------------------------------------------- transpose ----
-@pytest.mark.parametrize("case", ["qh768", "ash85", "random", "longcols", "wide", "big", "shortrows", "sparserows"])
+@pytest.mark.parametrize("case", CASES)
 def test_transpose_bit_exact(torch_cuda, sb, orc, case):
-    """Stable transpose, every path the default build takes: the MSD
-    partition passes + per-bucket final pass where n > 512 (pass A derives
-    each entry's row from rowptr and hands pass B one word of key bits and
-    row offset when the segments' row spans allow -- "sparserows" spans too
-    many rows, the device falls back; pass B hands the last pass one word of
-    row and low column bits; "longcols" gives few, long buckets; "big" 3M
-    columns), and the LSD passes on narrow matrices (qh768, ash85, "wide" is
-    n = 1e5 over 50 rows, "longcols" n = 40).  Colptr, row indices and values
-    bit-exact against orc_transpose (tranpose.h:6-43's stable scatter)."""
+    """Stable transpose, every form the library has (which one a case takes is
+    asserted on the CPU, test_transpose_shape_cpu.py).  MSD partition passes +
+    per-bucket last pass: pass A derives each entry's row from rowptr and
+    hands pass B one word of key bits and row offset when the segments' row
+    spans allow ("sparserows" spans too many rows, the device falls back);
+    pass B (128 digits; 256 on "sparserows") hands the last pass one word of
+    row and low column bits, or keys and rows apart where they do not fit a
+    word ("manyrows"); the last pass is lean ("random", "shortrows") or
+    staged, with a 3,072-entry tile (qh768, "wide", "sparserows", "manyrows",
+    and "big", whose pass-A workgroups walk 2 tiles each) or a 4,096-entry
+    tile ("longcols": n = 40, buckets of 2 columns).  LSD passes where n <=
+    512 (ash85: one pass, one tile; "narrow2tiles": 2 passes of 5 bits, 2
+    tiles) or n > 2^24 ("hugecols": 4 passes of 7 bits, 5 tiles).  Colptr, row
+    indices and values bit-exact against orc_transpose (tranpose.h:6-43's
+    stable scatter)."""
     torch = torch_cuda
-    rng = np.random.default_rng(5)
-    if case in ("qh768", "ash85"):
-        m, n, rp, col, val = sb.mm_read(os.path.join(GOLDEN, f"{case}.mtx"), 0)
-    elif case == "random":
-        m, n = 3000, 2500
-        rp, col, val = rand_csr(rng, m, n, 30)
-    elif case == "big":  # 2.2M nonzeros over 3M columns: 2 passes x 11 bits, 2 tiles per workgroup
-        m, n = 110000, 3_000_000
-        lens = rng.integers(0, 40, m)
-        rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        col = np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens]).astype(np.int32)
-        val = rng.standard_normal(int(rp[-1]))
-    elif case == "shortrows":  # 0-3 entries per row, half the rows empty: a 4096-entry tile
-        # holds thousands of row starts (pass A's row derivation takes several windows)
-        m, n = 200000, 5000
-        lens = rng.integers(0, 4, m) * (rng.random(m) < 0.5)
-        rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        col = np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens]).astype(np.int32)
-        val = rng.standard_normal(int(rp[-1]))
-    elif case == "sparserows":  # 2^24 columns (16 key bits past pass A) and one row in 100
-        # non-empty: a segment spans > 2^16 rows, so pass A cannot pack the row offset
-        m, n = 300000, 1 << 24
-        lens = np.where(rng.random(m) < 0.01, 5, 0)
-        rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        col = np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens]).astype(np.int32)
-        val = rng.standard_normal(int(rp[-1]))
-    elif case == "wide":  # more columns than rows, many empty columns
-        m, n = 50, 100000
-        rp, col, val = rand_csr(rng, m, n, 400, empty_frac=0.3)
-    else:  # columns longer than 32 / 4096 (medium and big sort paths)
-        m, n = 9000, 40
-        rp, col, val = rand_csr(rng, m, n, 40, empty_frac=0.2)
+    m, n, rp, col, val = transpose_case(sb, case, seed=5)
     nnz = int(rp[-1])
     cp, ri, cv = orc.transpose(m, n, rp, col, val)
     A = sb.DeviceCSR.upload(0, n, rp, col, val)
@@ -190,46 +154,14 @@ def test_transpose_bit_exact(torch_cuda, sb, orc, case):
     A.close()
 
 
-@pytest.mark.parametrize("shape", ["one_entry", "one_row", "one_col_tall", "last_col", "tile_edge",
-                                   "dup_free_dense_row", "empty_tail_rows"])
+@pytest.mark.parametrize("shape", EDGES)
 def test_transpose_edges(torch_cuda, sb, orc, shape):
-    """Edge shapes on the default MSD path (n > 512): a single nonzero, every
-    entry in one row, one populated column over many rows, entries only in the
-    last column, nnz exactly one tile / one past it, rows empty at the end."""
+    """Edge shapes on the MSD path (n = 5000: c = 8, 3 + 2 high bits, staged
+    last pass): a single nonzero, every entry in one row, one populated column
+    over many rows, entries only in the last column, nnz exactly one tile / one
+    past it, rows empty at the end."""
     torch = torch_cuda
-    rng = np.random.default_rng(7)
-    n = 5000
-    if shape == "one_entry":
-        m = 3
-        rp = np.array([0, 0, 1, 1], np.int64)
-        col = np.array([4321], np.int32)
-    elif shape == "one_row":
-        m = 1
-        col = np.sort(rng.choice(n, 3000, replace=False)).astype(np.int32)
-        rp = np.array([0, len(col)], np.int64)
-    elif shape == "one_col_tall":
-        m = 20000
-        rp = np.arange(m + 1, dtype=np.int64)
-        col = np.full(m, 777, np.int32)
-    elif shape == "last_col":
-        m = 4096
-        rp = np.arange(m + 1, dtype=np.int64)
-        col = np.full(m, n - 1, np.int32)
-    elif shape == "tile_edge":  # 4097 nonzeros: one full tile and one entry
-        m = 4097
-        rp = np.arange(m + 1, dtype=np.int64)
-        col = rng.integers(0, n, m).astype(np.int32)
-    elif shape == "dup_free_dense_row":  # every column of one row, then sparse rows
-        m = 700
-        lens = np.concatenate([[n], rng.integers(0, 5, m - 1)])
-        rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        col = np.concatenate([np.arange(n)] + [np.sort(rng.choice(n, L, replace=False)) for L in lens[1:]]).astype(np.int32)
-    else:  # empty_tail_rows
-        m = 50000
-        lens = np.concatenate([rng.integers(1, 6, 1000), np.zeros(m - 1000, np.int64)])
-        rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-        col = np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens[:1000]]).astype(np.int32)
-    val = rng.standard_normal(len(col))
+    m, n, rp, col, val = transpose_edge(shape)
     nnz = int(rp[-1])
     cp, ri, cv = orc.transpose(m, n, rp, col, val)
     A = sb.DeviceCSR.upload(0, n, rp, col, val)
@@ -244,23 +176,12 @@ def test_transpose_edges(torch_cuda, sb, orc, shape):
     assert np.array_equal(dcv.cpu().numpy()[:nnz], cv)
 
 
-@pytest.mark.parametrize("case", ["qh768", "ash85", "random", "longcols", "wide"])
+@pytest.mark.parametrize("case", MGPU_CASES)
 @pytest.mark.parametrize("ngpu", [1, 2, 3, 5])
 def test_transpose_mgpu_bit_exact(torch_cuda, sb, orc, case, ngpu):
     """Multi-device CSR -> CSC: blocks of whole rows, composed
     on device 0; indices and values bit-exact against the stable transpose."""
-    rng = np.random.default_rng(11)
-    if case in ("qh768", "ash85"):
-        m, n, rp, col, val = sb.mm_read(os.path.join(GOLDEN, f"{case}.mtx"), 0)
-    elif case == "random":
-        m, n = 3000, 2500
-        rp, col, val = rand_csr(rng, m, n, 30)
-    elif case == "longcols":
-        m, n = 9000, 40
-        rp, col, val = rand_csr(rng, m, n, 40, empty_frac=0.2)
-    else:  # more columns than rows, many empty columns
-        m, n = 50, 100000
-        rp, col, val = rand_csr(rng, m, n, 400, empty_frac=0.3)
+    m, n, rp, col, val = transpose_case(sb, case, seed=11)
     cp, ri, cv = orc.transpose(m, n, rp, col, val)
     gcp, gri, gcv, t1, t2 = sb.csr2csc_mgpu(m, n, rp, col, val, ngpu)
     assert np.array_equal(gcp, cp) and np.array_equal(gri, ri) and np.array_equal(gcv, cv)
