@@ -248,6 +248,43 @@ long long sblas_spmv_algorithmic_bytes(sblas_csr A, int beta_nonzero);
  * width at full speed, use a second handle. */
 int sblas_spmm(sblas_csr A, int n, double alpha, const double *d_B, int ldb,
                int b_layout, double beta, double *d_C, int ldc, void *stream);
+/* What sblas_spmm decides for an m x k host CSR (rowptr int64, m + 1 ascending
+ * 32-bit offsets; col in any order, duplicates allowed), for inspection and
+ * tests; needs no GPU and reads the test options "spmm_ctile" and
+ * "spmm_mfma_fill" as a plan build does.  The plan is the one a first call of
+ * width ncols_plan builds; the call described has width ncols, B of leading
+ * dimension ldb in b_layout (as sblas_spmm) at device address b_addr, and
+ * beta.  info[15]:
+ *   nmfma       16-row blocks on the MFMA tile (nnz >= fill * 16 * distinct
+ *               columns of the block; fill 0.08, none when fill > 1)
+ *   nsparse, sparse_nnz   the rows outside those blocks and their entries
+ *   rowform     the kernel of those rows: 0 none (no such row, or the C-tile
+ *               form), 1 wave per row, 2 workgroup per row (split-k:
+ *               sparse_nnz >= 256 * nsparse)
+ *   ctile       1: the column-sorted C-tile form serves the whole matrix (no
+ *               MFMA block, m > 0, and m <= 16384 with k >= 2^17 unless
+ *               "spmm_ctile" says 0 / 1; needs ct_supported)
+ *   ct_supported  the C-tile keys can hold the matrix: 8 XCDs x
+ *               2^(32 - rbits) columns in whole slabs
+ *   ns, nrb, R, rbits, wlog   C-tile layout: slab sets per XCD (32 / (nrb x
+ *               16-column groups of ncols_plan), at least 1), row blocks, rows
+ *               per block (<= 1204), key bits of the row, log2 of the slab width
+ *   direct      keys hold the global column (k <= 2^(32 - rbits))
+ *   fast        the C-tile kernel with 16-byte B loads at 32-bit offsets: row
+ *               stride even, ncols % 16 == 0, B 16-byte aligned, k * stride * 8
+ *               < 2^32 (stride and address are those of the row-major panel
+ *               when transposes_B)
+ *   transposes_B  b_layout 0: B is first copied into the handle's row-major panel
+ *   kbeta       beta != 0: C is read
+ * ns .. direct are 0 unless ctile, fast is 0 unless ctile.  Bad arguments are
+ * SBLAS_ERR_INVALID. */
+int sblas_spmm_shape_host(int m, int k, const long long *rowptr, const int *col, int ncols_plan,
+                          int ncols, long long ldb, int b_layout, unsigned long long b_addr,
+                          double beta, long long *info);
+/* The same 15 values from a handle: the plan fields of the built SpMM plan,
+ * and fast, transposes_B, kbeta of the handle's last launch (-1 before the
+ * first).  SBLAS_ERR_INVALID before the plan is built (the first sblas_spmm). */
+int sblas_spmm_info(sblas_csr A, long long *info);
 
 /* Device CSR -> CSC transpose of a handle; outputs DEVICE arrays sized
  * colptr[n+1], rowidx[nnz], cval[nnz]; row indices ascend within columns

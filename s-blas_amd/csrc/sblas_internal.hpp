@@ -174,6 +174,7 @@ struct SpmmPlan {
     // writes it to its (XCD, set) partial; a reduce adds the partials.
     int ct_ns = 0, ct_nrb = 0, ct_R = 0, ct_rbits = 0, ct_wlog = 0;
     bool ct_direct = false;              // keys hold the global column
+    bool ct_supported = false;           // the packed key can hold this matrix (whether or not the form is taken)
     bool ct_slots = false;               // units are column-run slots of <= 2 entries
     unsigned *ct_key2 = nullptr;         // slots: second entry's local row, ~0 if none
     double *ct_val2 = nullptr;
@@ -278,6 +279,7 @@ struct sblas_csr_s {
     mutable size_t spmm_bt_bytes = 0;
     mutable double *spmm_part = nullptr;
     mutable size_t spmm_part_bytes = 0;
+    mutable int spmm_last[3] = {-1, -1, -1};  // the last launch's fast, transposes_B, kbeta (sblas_spmm_info)
     long long plan_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // device bytes per algorithm's plan
     int auto_algo = 0;          // SBLAS_SPMV_AUTO's choice (capi.hip pick_algo), 0 = not yet
     bool deterministic = sblas::deterministic_default();  // bitwise-repeatable launches (xsort's ordered form)

@@ -404,32 +404,114 @@ __global__ __launch_bounds__(64 * kCtRedWaves) void k_spmm_ctreduce(const double
     }
 }
 
-// host: the C-tile layout.  Returns SBLAS_ERR_UNSUPPORTED (caller keeps the
-// other forms) when the packed key cannot hold XCD-local column and row.
-static int build_ctile(sblas_csr_s &A, const std::vector<int> &rp, const std::vector<int> &hcol,
-                       const std::vector<double> &hval, int ncols)
-{
-    SpmmPlan &P = A.mm;
-    const int m = A.m, k = A.n;
-    // slab width 2^wlog columns (11: 2048 B rows = 1 MiB of B per slab at n =
-    // 64) and tile rows: experiment builds (Makefile `alt`) set
-    // -DSBLAS_SPMM_CTW / -DSBLAS_SPMM_CTR
+// ---- the SpMM shape ---------------------------------------------------------
+// Every decision of the plan build (build_spmm_plan, build_ctile) and of a
+// launch (launch_spmm) is taken by the pure host functions of this section;
+// sblas_spmm_shape_host reports them for a host CSR without a GPU, and
+// sblas_spmm_info what a built plan and its last launch took.
 #ifndef SBLAS_SPMM_CTW
 #define SBLAS_SPMM_CTW 11
 #endif
 #ifndef SBLAS_SPMM_CTR
 #define SBLAS_SPMM_CTR kCtMaxRows
 #endif
-    const int wlog = std::max(4, std::min(20, SBLAS_SPMM_CTW));
-    const int rcap = kCtMaxRows;
-    const int rmax = std::max(16, std::min(rcap, (int)(SBLAS_SPMM_CTR)));
-    const int nrb = (m + rmax - 1) / rmax;
-    const int R = (m + nrb - 1) / nrb;
-    int rbits = 1;
-    while ((1 << rbits) < R) ++rbits;
-    const long long nslab = ((long long)k + (1LL << wlog) - 1) >> wlog;
-    const long long jc_max = ((nslab + 7) / 8) << wlog;  // XCD-local columns
-    if (rbits + 1 > 32 || jc_max > (1LL << (32 - rbits))) return SBLAS_ERR_UNSUPPORTED;
+
+// the test options a plan build reads ("spmm_mfma_fill", "spmm_ctile")
+struct SpmmOptions {
+    double fill = SpmmPlan{}.fill_thresh;
+    bool has_ct = false, ct = false;
+};
+
+static SpmmOptions spmm_options()
+{
+    SpmmOptions o;
+    double opt = 0.0;
+    if (test_option("spmm_mfma_fill", &opt)) o.fill = opt;
+    if (test_option("spmm_ctile", &opt)) {
+        o.has_ct = true;
+        o.ct = opt != 0.0;
+    }
+    return o;
+}
+
+// a 16-row block of nz entries over nU distinct columns takes the MFMA tile
+static bool spmm_block_dense(long long nz, size_t nU, double fill)
+{
+    return fill <= 1.0 && nU > 0 && (double)nz >= fill * 16.0 * (double)nU;
+}
+
+// The 16-row blocks: which are dense, and what the row kernels keep.  Blocks
+// are analysed in parallel (a sort per block); Us (optional) receives the
+// sorted column union of every dense block.
+struct SpmmBlocks {
+    std::vector<char> dense;
+    int nmfma = 0, nsparse = 0;
+    long long sparse_nnz = 0;
+};
+
+template <class RP>
+static SpmmBlocks spmm_blocks(int m, const RP *rp, const int *col, double fill, std::vector<std::vector<int>> *Us)
+{
+    SpmmBlocks S;
+    const int nblk = (m + 15) / 16;
+    S.dense.assign((size_t)nblk, 0);
+    if (Us) Us->assign((size_t)nblk, {});
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int b = 0; b < nblk; ++b) {
+        const int r0 = b * 16, r1 = std::min(m, r0 + 16);
+        std::vector<int> U(col + rp[r0], col + rp[r1]);
+        std::sort(U.begin(), U.end());
+        U.erase(std::unique(U.begin(), U.end()), U.end());
+        S.dense[(size_t)b] = spmm_block_dense((long long)(rp[r1] - rp[r0]), U.size(), fill);
+        if (Us && S.dense[(size_t)b]) (*Us)[(size_t)b] = std::move(U);
+    }
+    for (int b = 0; b < nblk; ++b) {
+        const int r0 = b * 16, r1 = std::min(m, r0 + 16);
+        if (S.dense[(size_t)b]) {
+            ++S.nmfma;
+        } else {
+            S.nsparse += r1 - r0;
+            S.sparse_nnz += (long long)(rp[r1] - rp[r0]);
+        }
+    }
+    return S;
+}
+
+// C-tile form: few rows (m <= 16,384: a tile of <= 1,204 rows per CU covers
+// them in <= 14 row blocks), B much taller than the L2s (k >= 2^17: >= 64 MiB
+// at n = 64), no MFMA blocks.  The test hook "spmm_ctile" = 0/1 overrides the
+// size rule (0: the row kernels).
+static bool spmm_wants_ctile(const SpmmOptions &o, int nmfma, int m, int k)
+{
+    if (o.has_ct) return o.ct && nmfma == 0 && m > 0;
+    return nmfma == 0 && m > 0 && m <= 16384 && k >= (1 << 17);
+}
+
+// The C-tile layout's sizes for an m x k matrix whose plan is built by a call
+// of width ncols.  supported = false when the packed key cannot hold
+// XCD-local column and row (the caller keeps the row forms).
+struct CtileShape {
+    bool supported = false;
+    int ns = 0, nrb = 0, R = 0, rbits = 0, wlog = 0;
+    bool direct = false;
+};
+
+static CtileShape spmm_ctile_shape(int m, int k, int ncols)
+{
+    CtileShape T;
+    if (m <= 0) return T;
+    // slab width 2^wlog columns (11: 2048 B rows = 1 MiB of B per slab at n =
+    // 64) and tile rows: experiment builds (Makefile `alt`) set
+    // -DSBLAS_SPMM_CTW / -DSBLAS_SPMM_CTR
+    T.wlog = std::max(4, std::min(20, SBLAS_SPMM_CTW));
+    const int rmax = std::max(16, std::min(kCtMaxRows, (int)(SBLAS_SPMM_CTR)));
+    T.nrb = (m + rmax - 1) / rmax;
+    T.R = (m + T.nrb - 1) / T.nrb;
+    T.rbits = 1;
+    while ((1 << T.rbits) < T.R) ++T.rbits;
+    const long long nslab = ((long long)k + (1LL << T.wlog) - 1) >> T.wlog;
+    const long long jc_max = ((nslab + 7) / 8) << T.wlog;  // XCD-local columns
+    T.supported = T.rbits + 1 <= 32 && jc_max <= (1LL << (32 - T.rbits));
     // slab sets per XCD: about one workgroup per CU (8 x ns x nrb x column
     // groups) for the C width of the call that builds the plan -- a rank of
     // a column split (16 or 32 columns) otherwise filled only 1/4 or 1/2 of
@@ -438,7 +520,51 @@ static int build_ctile(sblas_csr_s &A, const std::vector<int> &rp, const std::ve
     // rank slices: config 4's N = 8 row block 105 -> 127 us, twice the
     // partial slots for the reduce; profiles/r05/spmm_grid/)
     const int ncg = std::max(1, (ncols + kCtCols - 1) / kCtCols);
-    const int ns = std::max(1, 32 / (nrb * ncg));
+    T.ns = std::max(1, 32 / (T.nrb * ncg));
+    // direct keys (global column << rbits | row) when the column fits: the
+    // kernel then needs no slab arithmetic; sorting is the same order
+    T.direct = (long long)k <= (1LL << (32 - T.rbits));
+    return T;
+}
+
+// which row kernel serves the rows outside MFMA blocks: 0 none (the C-tile
+// form, or no such row), 1 wave per row, 2 workgroup per row (long rows on
+// average)
+static int spmm_rowform(bool ctile, int nrows, long long nnz_rows)
+{
+    if (ctile || nrows <= 0) return 0;
+    return nnz_rows >= 256LL * nrows ? 2 : 1;
+}
+
+// One call's choices.  A column-major B is transposed into the handle's
+// row-major panel (ld = n; a device allocation, so 16-B aligned whatever
+// b_addr is).  fast: the C-tile kernel's 16-B loads at 32-bit byte offsets.
+struct SpmmCall {
+    bool transposes_B = false, fast = false, kbeta = false;
+    long long ldr = 0;
+};
+
+static SpmmCall spmm_call_shape(bool ctile, int k, int n, long long ldb, int b_layout, unsigned long long b_addr,
+                                double beta)
+{
+    SpmmCall c;
+    c.transposes_B = b_layout == 0;
+    c.ldr = c.transposes_B ? (long long)n : ldb;
+    const unsigned long long addr = c.transposes_B ? 0ULL : b_addr;
+    c.fast = ctile && (c.ldr % 2 == 0) && (n % kCtCols == 0) && ((addr & 15) == 0) &&
+             (unsigned long long)k * (unsigned long long)c.ldr * 8ULL < (1ULL << 32);
+    c.kbeta = beta != 0.0;
+    return c;
+}
+
+// host: the C-tile layout of a supported shape T (spmm_ctile_shape)
+static int build_ctile(sblas_csr_s &A, const std::vector<int> &rp, const std::vector<int> &hcol,
+                       const std::vector<double> &hval, const CtileShape &T)
+{
+    SpmmPlan &P = A.mm;
+    const int m = A.m, k = A.n;
+    const int wlog = T.wlog, nrb = T.nrb, R = T.R, rbits = T.rbits, ns = T.ns;
+    const long long nslab = ((long long)k + (1LL << wlog) - 1) >> wlog;
     // per-slab entry counts -> contiguous sets of about equal entries per XCD
     std::vector<long long> scount((size_t)nslab, 0);
     for (long long e = 0; e < A.nnz; ++e) scount[(size_t)(hcol[(size_t)e] >> wlog)]++;
@@ -461,9 +587,7 @@ static int build_ctile(sblas_csr_s &A, const std::vector<int> &rp, const std::ve
     for (int r = 0; r < m; ++r)
         for (int e = rp[r]; e < rp[r + 1]; ++e) off[(size_t)bucket(r, hcol[e]) + 1]++;
     for (int b = 0; b < nbk; ++b) off[(size_t)b + 1] += off[(size_t)b];
-    // direct keys (global column << rbits | row) when the column fits: the
-    // kernel then needs no slab arithmetic; sorting is the same order
-    const bool direct = (long long)k <= (1LL << (32 - rbits));
+    const bool direct = T.direct;
     std::vector<unsigned long long> kv((size_t)std::max<long long>(A.nnz, 1));  // key << 32 | entry index
     {
         std::vector<long long> next(off.begin(), off.end() - 1);
@@ -611,8 +735,8 @@ int build_spmm_plan(sblas_csr_s &A, int ncols, hipStream_t s)
 {
     if (A.mm.ready) return SBLAS_OK;
     SpmmPlan &P = A.mm;
-    double opt = 0.0;
-    if (test_option("spmm_mfma_fill", &opt)) P.fill_thresh = opt;  // test hook
+    const SpmmOptions opts = spmm_options();  // test hooks
+    P.fill_thresh = opts.fill;
     const int m = A.m;
     const std::vector<int> &rp = A.h_rowptr;
     std::vector<int> hcol((size_t)A.nnz);
@@ -623,31 +747,17 @@ int build_spmm_plan(sblas_csr_s &A, int ncols, hipStream_t s)
     }
     std::vector<int> mblock, mchunk{0}, ucol, srows;
     std::vector<double> atile;
-    P.sparse_nnz = 0;
 
     // 16-row blocks: the distinct columns of each (sorted) decide whether the
-    // block is dense enough for the MFMA tile; blocks are analysed in parallel
-    // (a sort per block), then assembled in block order
+    // block is dense enough for the MFMA tile; assembled in block order
     const int nblk = (m + 15) / 16;
-    std::vector<std::vector<int>> Us((size_t)nblk);
-    std::vector<char> dense((size_t)nblk, 0);
-#pragma omp parallel for schedule(dynamic, 4)
+    std::vector<std::vector<int>> Us;
+    const SpmmBlocks S = spmm_blocks(m, rp.data(), hcol.data(), P.fill_thresh, &Us);
+    const std::vector<char> &dense = S.dense;
     for (int b = 0; b < nblk; ++b) {
         const int r0 = b * 16, r1 = std::min(m, r0 + 16);
-        std::vector<int> U(hcol.begin() + rp[r0], hcol.begin() + rp[r1]);
-        std::sort(U.begin(), U.end());
-        U.erase(std::unique(U.begin(), U.end()), U.end());
-        const long long nz = rp[r1] - rp[r0];
-        dense[(size_t)b] = P.fill_thresh <= 1.0 && !U.empty() &&
-                           (double)nz >= P.fill_thresh * 16.0 * (double)U.size();
-        if (dense[(size_t)b]) Us[(size_t)b] = std::move(U);
-    }
-    for (int b = 0; b < nblk; ++b) {
-        const int r0 = b * 16, r1 = std::min(m, r0 + 16);
-        const long long nz = rp[r1] - rp[r0];
         if (!dense[(size_t)b]) {
             for (int r = r0; r < r1; ++r) srows.push_back(r);
-            P.sparse_nnz += nz;
             continue;
         }
         const std::vector<int> &U = Us[(size_t)b];
@@ -664,8 +774,9 @@ int build_spmm_plan(sblas_csr_s &A, int ncols, hipStream_t s)
         mblock.push_back(b);
         mchunk.push_back(mchunk.back() + nch);
     }
-    P.nmfma = (int)mblock.size();
-    P.nsparse = (int)srows.size();
+    P.nmfma = S.nmfma;
+    P.nsparse = S.nsparse;
+    P.sparse_nnz = S.sparse_nnz;
     auto up = [&](auto **dst, const auto &v) -> int {
         using T = typename std::decay_t<decltype(v)>::value_type;
         SBLAS_HIP(hipMalloc(dst, sizeof(T) * std::max<size_t>(v.size(), 1)));
@@ -677,16 +788,9 @@ int build_spmm_plan(sblas_csr_s &A, int ncols, hipStream_t s)
     SBLAS_TRY(up(&P.ucol, ucol));
     SBLAS_TRY(up(&P.atile, atile));
     SBLAS_TRY(up(&P.srows, srows));
-    // C-tile form: few rows (m <= 16,384: a tile of <= 1,204 rows per CU
-    // covers them in <= 14 row blocks), B much taller than the L2s (k >=
-    // 2^17: >= 64 MiB at n = 64), no MFMA blocks.  The test hook
-    // "spmm_ctile" = 0/1 overrides the size rule (0: the row-wave kernels).
-    bool ct = P.nmfma == 0 && m > 0 && m <= 16384 && A.n >= (1 << 17);
-    if (test_option("spmm_ctile", &opt)) ct = opt != 0.0 && P.nmfma == 0 && m > 0;
-    if (ct) {
-        const int rc = build_ctile(A, rp, hcol, hval, ncols);
-        if (rc != SBLAS_OK && rc != SBLAS_ERR_UNSUPPORTED) return rc;
-    }
+    const CtileShape T = spmm_ctile_shape(m, A.n, ncols);
+    P.ct_supported = T.supported;
+    if (spmm_wants_ctile(opts, P.nmfma, m, A.n) && T.supported) SBLAS_TRY(build_ctile(A, rp, hcol, hval, T));
     (void)s;
     P.ready = true;
     return SBLAS_OK;
@@ -742,20 +846,24 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B, int 
                 int b_layout, double beta, double *C, int ldc, hipStream_t s)
 {
     if (A.m == 0 || n == 0) return SBLAS_OK;
+    const SpmmPlan &P = A.mm;
+    const bool ctile = P.ready && P.ct_nrb > 0;
+    const SpmmCall call = spmm_call_shape(ctile, A.n, n, ldb, b_layout, (unsigned long long)(uintptr_t)B, beta);
+    A.spmm_last[0] = call.fast;
+    A.spmm_last[1] = call.transposes_B;
+    A.spmm_last[2] = call.kbeta;
     const double *Brow = B;
-    long long ldr = ldb;
-    if (b_layout == 0) {
+    const long long ldr = call.ldr;
+    if (call.transposes_B) {
         SBLAS_TRY(grow_scratch(A.spmm_bt, A.spmm_bt_bytes, sizeof(double) * (size_t)A.n * (size_t)n));
         if (A.n > 0) {
             dim3 grid((A.n + 63) / 64, (n + 63) / 64);
             hipLaunchKernelGGL(k_transpose_B, grid, dim3(256), 0, s, B, (long long)ldb, A.n, n, A.spmm_bt);
         }
         Brow = A.spmm_bt;
-        ldr = n;
     }
-    const SpmmPlan &P = A.mm;
     const int nslab = (n + 63) / 64;
-    if (P.ready && P.ct_nrb > 0) {
+    if (ctile) {
         const int ncg = (n + kCtCols - 1) / kCtCols;
         const int nslot = 8 * P.ct_ns;
         SBLAS_TRY(grow_scratch(A.spmm_part, A.spmm_part_bytes,
@@ -775,8 +883,7 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B, int 
                                               (int)(sizeof(double) * kCtMaxRows * kCtPad)));
             attr_set[A.device & 63] = true;
         }
-        const bool fast = (ldr % 2 == 0) && (n % kCtCols == 0) && (((uintptr_t)Brow & 15) == 0) &&
-                          (unsigned long long)A.n * (unsigned long long)ldr * 8ULL < (1ULL << 32);
+        const bool fast = call.fast;
         using K = void (*)(const unsigned *, const double *, const unsigned *, const double *, const long long *,
                            int, int, int, int, int, int, const double *, long long, int, int, double *);
         K kern;
@@ -790,7 +897,7 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B, int 
                            P.ct_val2, P.ct_off, P.ct_ns, P.ct_nrb, P.ct_R, P.ct_rbits, P.ct_wlog, ncg, Brow, ldr,
                            n, A.m, part);
         const unsigned nb = (unsigned)(((long long)A.m * n + 63) / 64);
-        if (beta != 0.0)
+        if (call.kbeta)
             hipLaunchKernelGGL(k_spmm_ctreduce<true>, dim3(nb), dim3(64 * kCtRedWaves), 0, s, part, nslot, A.m, n,
                                alpha, beta, C, (long long)ldc);
         else
@@ -802,21 +909,19 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B, int 
     // rows of sparse blocks (all rows when no plan / no dense block)
     const int nrows = P.ready ? P.nsparse : A.m;
     const int *rows = P.ready ? P.srows : nullptr;
-    // long rows on average -> a workgroup per (row, slab)
-    const long long nnz_rows = P.ready ? P.sparse_nnz : A.nnz;
-    const bool splitk = nrows > 0 && nnz_rows >= 256LL * nrows;
-    if (splitk) {
+    const int rowform = spmm_rowform(false, nrows, P.ready ? P.sparse_nnz : A.nnz);
+    if (rowform == 2) {
         const unsigned nb = (unsigned)((long long)nrows * nslab);
-        if (beta != 0.0)
+        if (call.kbeta)
             hipLaunchKernelGGL(k_spmm_rowsplitk<true>, dim3(nb), dim3(256), 0, s, A.rowptr, A.rowptr + 1,
                                A.col, A.val, Brow, ldr, nrows, n, nslab, alpha, beta, C, (long long)ldc, rows);
         else
             hipLaunchKernelGGL(k_spmm_rowsplitk<false>, dim3(nb), dim3(256), 0, s, A.rowptr, A.rowptr + 1,
                                A.col, A.val, Brow, ldr, nrows, n, nslab, alpha, beta, C, (long long)ldc, rows);
-    } else if (nrows > 0) {
+    } else if (rowform == 1) {
         const long long waves = (long long)nrows * nslab;
         const unsigned nb = (unsigned)((waves + 3) / 4);
-        if (beta != 0.0)
+        if (call.kbeta)
             hipLaunchKernelGGL(k_spmm_rowwave<true>, dim3(nb), dim3(256), 0, s, A.rowptr, A.col, A.val,
                                Brow, ldr, nrows, n, nslab, alpha, beta, C, (long long)ldc, rows);
         else
@@ -826,7 +931,7 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B, int 
     if (P.ready && P.nmfma > 0) {
         const long long waves = (long long)P.nmfma * nslab;
         const unsigned nb = (unsigned)((waves + 3) / 4);
-        if (beta != 0.0)
+        if (call.kbeta)
             hipLaunchKernelGGL(k_spmm_mfma<true>, dim3(nb), dim3(256), 0, s, P.mblock, P.mchunk, P.ucol,
                                P.atile, P.nmfma, Brow, ldr, A.m, n, nslab, alpha, beta, C,
                                (long long)ldc);
@@ -840,3 +945,39 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B, int 
 }
 
 }  // namespace sblas
+
+extern "C" int sblas_spmm_shape_host(int m, int k, const long long *rowptr, const int *col, int ncols_plan,
+                                     int ncols, long long ldb, int b_layout, unsigned long long b_addr,
+                                     double beta, long long *info)
+{
+    using namespace sblas;
+    if (m < 0 || k < 0 || !rowptr || !info || ncols_plan < 0 || ncols < 0 || (b_layout != 0 && b_layout != 1))
+        return SBLAS_ERR_INVALID;
+    if (rowptr[0] != 0 || rowptr[m] > INT_MAX || (rowptr[m] > 0 && !col)) return SBLAS_ERR_INVALID;
+    for (int r = 0; r < m; ++r)
+        if (rowptr[r + 1] < rowptr[r]) return SBLAS_ERR_INVALID;
+    const SpmmOptions opts = spmm_options();
+    const SpmmBlocks S = spmm_blocks(m, rowptr, col, opts.fill, nullptr);
+    const CtileShape T = spmm_ctile_shape(m, k, ncols_plan);
+    const bool ctile = spmm_wants_ctile(opts, S.nmfma, m, k) && T.supported;
+    const SpmmCall c = spmm_call_shape(ctile, k, ncols, ldb, b_layout, b_addr, beta);
+    const long long v[15] = {S.nmfma, S.nsparse, S.sparse_nnz, spmm_rowform(ctile, S.nsparse, S.sparse_nnz),
+                             ctile ? 1 : 0, T.supported ? 1 : 0, ctile ? T.ns : 0, ctile ? T.nrb : 0,
+                             ctile ? T.R : 0, ctile ? T.rbits : 0, ctile ? T.wlog : 0, ctile && T.direct ? 1 : 0,
+                             c.fast ? 1 : 0, c.transposes_B ? 1 : 0, c.kbeta ? 1 : 0};
+    for (int i = 0; i < 15; ++i) info[i] = v[i];
+    return SBLAS_OK;
+}
+
+extern "C" int sblas_spmm_info(sblas_csr A, long long *info)
+{
+    using namespace sblas;
+    if (!A || !info || !A->mm.ready) return SBLAS_ERR_INVALID;
+    const SpmmPlan &P = A->mm;
+    const bool ctile = P.ct_nrb > 0;
+    const long long v[15] = {P.nmfma, P.nsparse, P.sparse_nnz, spmm_rowform(ctile, P.nsparse, P.sparse_nnz),
+                             ctile ? 1 : 0, P.ct_supported ? 1 : 0, P.ct_ns, P.ct_nrb, P.ct_R, P.ct_rbits, P.ct_wlog,
+                             P.ct_direct ? 1 : 0, A->spmm_last[0], A->spmm_last[1], A->spmm_last[2]};
+    for (int i = 0; i < 15; ++i) info[i] = v[i];
+    return SBLAS_OK;
+}

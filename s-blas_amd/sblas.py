@@ -121,6 +121,8 @@ _sig("sblas_csr_set_deterministic", _i, _p, _i)
 _sig("sblas_csr_xsort_info", _i, _p, _p)
 _sig("sblas_xsort_plan_host", _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _ll, _p, _ll)
 _sig("sblas_transpose_shape_host", _i, _i, _i, _ll, _i, _p)
+_sig("sblas_spmm_shape_host", _i, _i, _i, _p, _p, _i, _i, _ll, _i, C.c_ulonglong, _d, _p)
+_sig("sblas_spmm_info", _i, _p, _p)
 _sig("sblas_csr_get_deterministic", _i, _p, _p)
 _sig("sblas_csr_xsort_export", _i, _p, _i, _p, _ll, _p)
 _sig("sblas_csr_xsort_build_info", _i, _p, _p)
@@ -269,6 +271,29 @@ def transpose_shape_host(m: int, n: int, nnz: int, ncu: int) -> dict:
     keys = ("msd", "c", "bA", "bB", "passes", "rb", "ntiles", "S", "nwg", "JB", "nwgB", "packA", "pack", "nbC",
             "ftile", "lean", "fgrid", "ncnt")
     return {k: int(v) for k, v in zip(keys, info)}
+
+
+SPMM_SHAPE_KEYS = ("nmfma", "nsparse", "sparse_nnz", "rowform", "ctile", "ct_supported", "ns", "nrb", "R", "rbits",
+                   "wlog", "direct", "fast", "transposes_B", "kbeta")
+
+
+def spmm_shape_host(k: int, rowptr, col, ncols_plan: int, ncols: int = None, ldb: int = None, b_layout: int = 1,
+                    b_addr: int = 0, beta: float = 1.0) -> dict:
+    """What sblas_spmm decides for a host CSR of k columns (sblas_spmm_shape_host;
+    no GPU; reads the test options spmm_ctile and spmm_mfma_fill): the plan a
+    first call of width ncols_plan builds, and the call of width ncols (default
+    ncols_plan) with B of leading dimension ldb (default: the packed one) in
+    b_layout at address b_addr.  Keys: SPMM_SHAPE_KEYS."""
+    rp = np.ascontiguousarray(rowptr, np.int64)
+    cl = np.ascontiguousarray(col, np.int32)
+    m = len(rp) - 1
+    n = ncols_plan if ncols is None else ncols
+    if ldb is None:
+        ldb = n if b_layout == 1 else k
+    info = np.zeros(len(SPMM_SHAPE_KEYS), np.int64)
+    check(lib.sblas_spmm_shape_host(m, k, ptr(rp), ptr(cl), ncols_plan, n, ldb, b_layout, b_addr, float(beta),
+                                    ptr(info)), "spmm_shape_host")
+    return {key: int(v) for key, v in zip(SPMM_SHAPE_KEYS, info)}
 
 
 def coo_sortbyrow(m: int, row, col, val):
@@ -583,6 +608,13 @@ class DeviceCSR:
              c_ptr: int, ldc: int, stream=None) -> None:
         check(lib.sblas_spmm(self.h, ncols, alpha, b_ptr, ldb, b_layout, beta, c_ptr, ldc,
                              stream), "spmm")
+
+    def spmm_info(self) -> dict:
+        """The built SpMM plan's shape and the last launch's fast, transposes_B,
+        kbeta (sblas_spmm_info; keys as spmm_shape_host)."""
+        v = np.zeros(len(SPMM_SHAPE_KEYS), np.int64)
+        check(lib.sblas_spmm_info(self.h, ptr(v)), "spmm_info")
+        return {key: int(x) for key, x in zip(SPMM_SHAPE_KEYS, v)}
 
     def transpose(self, colptr_ptr: int, rowidx_ptr: int, cval_ptr: int, stream=None) -> None:
         check(lib.sblas_csr_transpose(self.h, colptr_ptr, rowidx_ptr, cval_ptr, stream),

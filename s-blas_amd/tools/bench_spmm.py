@@ -254,7 +254,7 @@ def main():
                        "structure": (f"{args.points}-point 3-D stencil {args.stencil}^3" if args.stencil
                                      else f"blocky{args.blocky}" if args.blocky
                                      else "rail4284-shaped uniform random"),
-                       "mfma_blocks": int(op.A.spmm_info()[0]) if hasattr(op.A, "spmm_info") else None,
+                       "mfma_blocks": op.A.spmm_info()["nmfma"],
                        "partition": ("single GPU" if world == 1 else
                                      "whole-row blocks by nnz, B replicated, C all-gathered"
                                      if args.split == "rows" else

@@ -5,36 +5,28 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from spmm_cases import FORM_KERNELS, FORM_OPTS, block_dense_csr, spmm_bound, spmm_matrix
 from transpose_cases import CASES, EDGES, MGPU_CASES, rand_csr, transpose_case, transpose_edge
 
 pytestmark = pytest.mark.gpu
 
 
 # ---------------------------------------------------------------- SpMM ----
-def spmm_bound(rp, col, val, B, alpha, beta, C0):
-    u = 2.0 ** -53
-    m = len(rp) - 1
-    k = np.diff(rp).astype(np.float64)
-    gam = (k * u / (1 - k * u))[:, None]
-    rows = np.repeat(np.arange(m), np.diff(rp))
-    S = np.zeros((m, B.shape[1]))
-    np.add.at(S, rows, np.abs(alpha * val[:, None] * B[col, :]))
-    return 4 * gam * S + 4 * u * np.abs(beta * C0) + 1e-300
-
-
 @pytest.mark.parametrize("form", ["rowwave", "splitk", "ct", "ctrows"])
 @pytest.mark.parametrize("ncols", [1, 16, 64, 100])
 @pytest.mark.parametrize("layout", [0, 1])
 def test_spmm(torch_cuda, sb, orc, ncols, layout, form):
     """Both row kernels: wave per row ("rowwave") and workgroup per row split
     over its nonzeros (picked for rows of >= 256 entries on average:
-    "splitk", 60 rows of ~1,000), and the column-sorted C-tile form (test
-    option spmm_ctile=1: "ct" = 3 slabs of 2048 columns, one slab set;
-    "ctrows" = 2,500 rows, i.e. 3 row blocks of 834)."""
+    "splitk", 60 rows of ~1,000; its 16-row blocks fill more than 8% of their
+    column unions, so the test option spmm_mfma_fill=2 keeps them off the MFMA
+    tile, which would otherwise take every row), and the column-sorted C-tile
+    form (test option spmm_ctile=1: "ct" = 3 slabs of 2048 columns; "ctrows" =
+    2,500 rows, i.e. 3 row blocks of 834).  Every parameter set asserts the
+    kernels it ran (spmm_cases.FORM_KERNELS) through spmm_info()."""
     torch = torch_cuda
     rng = np.random.default_rng(ncols + 10 * layout)
-    m, k = {"ctrows": 2500, "splitk": 60}.get(form, 700), 5000
-    rp, col, val = rand_csr(rng, m, k, 2000 if form == "splitk" else 50, long_rows=[(3, 3000)])
+    m, k, rp, col, val = spmm_matrix(form, rng)
     B = rng.standard_normal((k, ncols))
     C0 = rng.standard_normal((m, ncols))
     alpha, beta = -0.7, 0.8  # dspmm_baseline_test.cu:518-519
@@ -47,9 +39,12 @@ def test_spmm(torch_cuda, sb, orc, ncols, layout, form):
         Bd = torch.from_numpy(np.ascontiguousarray(B).ravel()).cuda()
         ldb = ncols
     Cd = torch.from_numpy(np.asfortranarray(C0).ravel(order="F")).cuda()
-    with sb.test_options(**({"spmm_ctile": 1} if form.startswith("ct") else {})):  # the plan builds here
+    with sb.test_options(**FORM_OPTS[form]):  # the plan builds here
         A.spmm(ncols, alpha, Bd.data_ptr(), ldb, layout, beta, Cd.data_ptr(), m)
     torch.cuda.synchronize()
+    T = A.spmm_info()
+    assert (T["rowform"], T["ctile"], T["nmfma"]) == FORM_KERNELS[form]
+    assert (T["transposes_B"], T["kbeta"]) == (int(layout == 0), 1)
     got = Cd.cpu().numpy().reshape((ncols, m)).T
     assert np.all(np.abs(got - want) <= spmm_bound(rp, col, val, B, alpha, beta, C0))
     A.close()
@@ -622,23 +617,6 @@ def test_assemble_slices(torch_cuda, sb):
 
 
 # ------------------------------------------------------- SpMM MFMA tiles ----
-def block_dense_csr(rng, nblk, width, k, sparse_tail=0):
-    """16-row blocks, each dense over `width` random columns (MFMA path), plus
-    `sparse_tail` random sparse rows (row-wave path)."""
-    rows = []
-    for _ in range(nblk):
-        cols = np.sort(rng.choice(k, width, replace=False))
-        for _ in range(16):
-            keep = cols[rng.random(width) < 0.9]  # ~90% fill
-            rows.append(keep)
-    for _ in range(sparse_tail):
-        rows.append(np.sort(rng.choice(k, 20, replace=False)))
-    lens = np.array([len(r) for r in rows])
-    rp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
-    col = np.concatenate(rows).astype(np.int32)
-    return rp, col, rng.standard_normal(int(rp[-1]))
-
-
 @pytest.mark.parametrize("fill", ["default", "0", "2"])
 @pytest.mark.parametrize("ncols", [64, 40, 130])
 def test_spmm_mfma_tiles(torch_cuda, sb, orc, fill, ncols):
@@ -658,6 +636,9 @@ def test_spmm_mfma_tiles(torch_cuda, sb, orc, fill, ncols):
     with sb.test_options(**({} if fill == "default" else {"spmm_mfma_fill": float(fill)})):
         A.spmm(ncols, 0.75, Bd.data_ptr(), ncols, 1, -0.5, Cd.data_ptr(), m)
     torch.cuda.synchronize()
+    T = A.spmm_info()  # 12 dense blocks, 21 tail rows (blocks 12, 13: dense only at fill 0)
+    assert (T["nmfma"], T["nsparse"], T["rowform"], T["ctile"]) == {"default": (12, 21, 1, 0), "0": (14, 0, 0, 0),
+                                                                    "2": (0, 213, 1, 0)}[fill]
     got = Cd.cpu().numpy().reshape((ncols, m)).T
     # MFMA sums the dense tile in union-column order (the rows' own order here,
     # columns are sorted) with exact zeros for the holes: same bound applies
