@@ -340,6 +340,35 @@ int sblas_trsv_solve_rhs(sblas_trsv T, int rhs, const double *d_b, double *d_x, 
  * arrival order: within the fp64 bound, not bitwise repeatable. */
 int sblas_trsv_solve_rhs_opt(sblas_trsv T, int algo, int opt, int rhs, const double *d_b,
                              double *d_x, void *stream);
+/* What a solve decides before its launch, for inspection and tests; needs no
+ * GPU.  algo 0..3 as sblas_trsv_solve (4 is SBLAS_ERR_INVALID: its choice
+ * needs the device probe); opt the push lane mapping (1..3; 0 = the rhs 1
+ * push of sblas_trsv_solve; ignored unless algo 0); mgpu 1 = a block of the
+ * multi-GPU solve (algo 1 only) among `blocks` blocks, blocks_on_device of
+ * them on its device (0: one handle, blocks = blocks_on_device = 1); ncu the
+ * device's CUs.  info[11]: executor (0 push, 1 pull, 2 level-set),
+ * level_order (tickets / rows in level order), c (pass width: rhs rounded up
+ * to a power of two, <= 64), rp, v (lanes per row, right-hand sides per lane:
+ * the pull kernel instance), passes (ceil(rhs / (rp * v))), rows_per_claim
+ * (64 / rp; push: 1), sys (x polled and published at system scope), threads
+ * (per workgroup), grid (workgroups; level-set: of a run of wide levels, a
+ * run of narrow ones is one workgroup), slp (poll back-off: >= 0 sleeps of
+ * slp x 64 clocks, < 0 adaptive up to 2^-slp).  c .. passes, sys and slp are 0
+ * for the push and level-set executors.  Bad arguments are
+ * SBLAS_ERR_INVALID. */
+int sblas_trsv_shape_host(int algo, int opt, int rhs, int mgpu, int blocks, int blocks_on_device,
+                          int ncu, long long *info);
+/* The level analysis of a HOST CSC triangle (layout as sblas_trsv_create),
+ * no GPU.  info[4]: levels, rows of the widest level, and the level-set
+ * executor's schedule: runs of narrow levels (<= 2048 rows each; one
+ * workgroup per run) and runs of wide levels (one persistent grid per run). */
+int sblas_trsv_levels_host(int n, const int *colptr, const int *rowidx, int substitution,
+                           long long *info);
+/* The shape of the handle's last solve: info[13], the 11 values of
+ * sblas_trsv_shape_host, then the narrow and the wide runs of the level
+ * schedule (0 unless the executor is the level-set one).
+ * SBLAS_ERR_INVALID before the first solve. */
+int sblas_trsv_info(sblas_trsv T, long long *info);
 /* Out-of-core SpMV (the task pool + streams of spMV_mgpu_v2,
  * dspmv_mgpu_v2.cu:33-441).  HOST CSR (int64 rowptr), x and y: the matrix is
  * streamed through ngpu devices in nnz-balanced chunks of chunk_nnz, over
@@ -399,6 +428,9 @@ int sblas_trsv_mgpu_run(sblas_trsv_mgpu h, const double *b, double *x, double *s
 /* Where the blocks run: block d's physical device and row count (arrays of
  * *nblocks entries; any may be NULL). */
 int sblas_trsv_mgpu_info(sblas_trsv_mgpu h, int *nblocks, int *block_device, int *block_rows);
+/* Block 0's shape in the last run: info[11] as sblas_trsv_shape_host.
+ * SBLAS_ERR_INVALID before the first run. */
+int sblas_trsv_mgpu_shape(sblas_trsv_mgpu h, long long *info);
 int sblas_trsv_mgpu_destroy(sblas_trsv_mgpu h);
 /* create fails with SBLAS_ERR_UNSUPPORTED (or SBLAS_ERR_HIP) before anything
  * is launched when two of its devices have no peer access (producers store

@@ -23,6 +23,9 @@
 //     sums are deterministic.  One LANE per row; lanes never block inside an
 //     iteration, so rows that depend on rows of the same wave resolve across
 //     iterations.
+//
+// Everything decided on the host before a launch is trsv_shape
+// (sptrsv_shape.cpp); every launch site below launches from it.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -31,6 +34,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sblas_internal.hpp"
+#include "sptrsv_shape.hpp"
 
 struct sblas_trsv_s {
     int device = 0;
@@ -51,17 +55,20 @@ struct sblas_trsv_s {
     unsigned *ctl = nullptr;   // [0] ticket, [kAbort] timeout flag (kCtlBytes block)
     int nlevels = -1;
     int auto_algo = 0;         // sblas_trsv_solve algo 4: the pull executor's ticket order (1 or 3)
-    int pull_threads = 0;      // fixed at create (0: by ticket order, pull_threads())
     // level-set executor (algo 2), built on its first solve: rows in level
     // order (stable by row), the CSR rows copied into that order, level
-    // pointers, and the launch schedule (runs of narrow levels -> one
-    // workgroup with barriers; each wide level -> one grid launch)
+    // pointers, and the launch schedule (a run of narrow levels -> one
+    // workgroup with barriers; a run of wide levels -> one persistent grid
+    // with grid barriers)
     int *lrow = nullptr, *lrp = nullptr, *lcol = nullptr;
     double *lval = nullptr;
     int *lptr_d = nullptr;
     unsigned *larrive = nullptr;            // grid barrier: arrival epoch per workgroup
     std::vector<int> lptr;                  // host copy [nlevels + 1]
-    std::vector<std::pair<int, int>> lsched;  // (first level, end level); end < 0: wide level
+    std::vector<sblas::TrsvRun> lsched;
+    // the last solve's shape (sblas_trsv_info)
+    bool solved = false;
+    sblas::TrsvShape last{};
 };
 
 namespace sblas {
@@ -183,7 +190,7 @@ __device__ __forceinline__ unsigned long long ld_sc1_u64(const unsigned long lon
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// Poll back-off of a wave whose lanes all still wait (SBLAS_TRSV_SLEEP):
+// Poll back-off of a wave whose lanes all still wait (TrsvShape::slp):
 // slp >= 0 sleeps slp x 64 clocks after every poll; slp < 0 doubles the
 // sleep after each poll on which no lane of the wave advanced, up to 2^-slp,
 // and drops it back to one on progress.  Every polling lane is an L2 request
@@ -439,7 +446,7 @@ struct TrsmArgs {
     unsigned long long *const *xs;        // [g] peers' x (only q > d used); null if g == 1
     int g, d, o0, nloc, n, rhs, backward, by_row;
     const int *lrow;                      // level order (algo 3): ticket t is row lrow[t], CSR row t; else null
-    int slp;                              // poll back-off (k_trsv_pull's SBLAS_TRSV_SLEEP units)
+    int slp;                              // poll back-off (trsv_backoff)
 };
 
 // RP lanes per row, each lane V right-hand sides RP apart (a pass covers
@@ -598,62 +605,35 @@ __global__ __launch_bounds__(256) void k_trsm_pull(const TrsmArgs P, unsigned *c
     }
 }
 
-// Right-hand sides per lane for pass width c (rhs rounded up to a power of
-// two, <= 64).  Measured (r03_trsm_v3, ms; config-5 stand-in natural order /
-// 27-point 100^3 stencil level order):
-//   rhs   V=1          V=2          V=4          V=8
-//    4    4.22 / 3.01  3.21 / 3.50  4.95 / 8.19  4.95 / 8.19
-//    8    8.21 / 3.14  4.29 / 3.30  4.61 / 5.68  8.29 / 19.2
-//   16   16.2  / 3.81  8.25 / 3.51  6.48 / 5.10  7.58 / 13.2
-//   32   32.2  / 6.32  16.3 / 3.85  10.2 / 5.01  10.2 / 8.54
-//   64   64.3  / 11.8  32.6 / 6.38  17.2 / 4.94  16.0 / 7.94
-// Natural order is bound by the ticket counter (~85 M claims/s, one claim
-// per 64 / RP rows) up to V = 4: wider lanes, fewer claims.  In level order a
-// wave's rows are independent rows of one level and longer per-lane rows
-// lengthen every level.  An experiment build (Makefile `alt`,
-// -DSBLAS_TRSM_V=v) fixes V.
-static int trsm_cols_per_lane(int c, bool level)
-{
-#ifdef SBLAS_TRSM_V
-    (void)c;
-    (void)level;
-    return SBLAS_TRSM_V >= 8 ? 8 : SBLAS_TRSM_V >= 4 ? 4 : SBLAS_TRSM_V >= 2 ? 2 : 1;
-#endif
-    if (level) return c <= 8 ? 1 : c <= 32 ? 2 : 4;
-    return c <= 8 ? 2 : c <= 32 ? 4 : 8;
-}
+// The SpTRSM instances that trsv_shape can ask for: the six natural-order
+// (RP, V) pairs at both scopes, the six level-order pairs at agent scope
+// (level order is single-device).  Anything else is a bug.
+using PullKernel = void (*)(const TrsmArgs, unsigned *);
+struct PullEntry {
+    int rp, v;
+    PullKernel agent, sys;
+};
+#define SBLAS_PULL_BOTH(RP, V) {RP, V, k_trsm_pull<RP, V, false>, k_trsm_pull<RP, V, true>}
+#define SBLAS_PULL_AGENT(RP, V) {RP, V, k_trsm_pull<RP, V, false>, nullptr}
+static const PullEntry kPullTable[] = {
+    SBLAS_PULL_BOTH(1, 2),  SBLAS_PULL_BOTH(2, 2),  SBLAS_PULL_BOTH(4, 2),
+    SBLAS_PULL_BOTH(4, 4),  SBLAS_PULL_BOTH(8, 4),  SBLAS_PULL_BOTH(8, 8),
+    SBLAS_PULL_AGENT(2, 1), SBLAS_PULL_AGENT(4, 1), SBLAS_PULL_AGENT(8, 1),
+    SBLAS_PULL_AGENT(8, 2), SBLAS_PULL_AGENT(16, 2), SBLAS_PULL_AGENT(16, 4),
+};
+#undef SBLAS_PULL_BOTH
+#undef SBLAS_PULL_AGENT
 
-template <int V, bool kSys>
-static void launch_trsm_v(int rp, const TrsmArgs &P, unsigned *ctl, int grid, hipStream_t s)
+static int launch_trsm(const TrsvShape &S, const TrsmArgs &P, unsigned *ctl, hipStream_t s)
 {
-    switch (rp) {
-    case 1: hipLaunchKernelGGL((k_trsm_pull<1, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
-    case 2: hipLaunchKernelGGL((k_trsm_pull<2, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
-    case 4: hipLaunchKernelGGL((k_trsm_pull<4, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
-    case 8: hipLaunchKernelGGL((k_trsm_pull<8, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
-    case 16: hipLaunchKernelGGL((k_trsm_pull<16, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
-    case 32: hipLaunchKernelGGL((k_trsm_pull<32, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
-    default: hipLaunchKernelGGL((k_trsm_pull<64, V, kSys>), dim3(grid), dim3(256), 0, s, P, ctl); break;
+    for (const PullEntry &e : kPullTable) {
+        PullKernel k = S.sys ? e.sys : e.agent;
+        if (e.rp != S.rp || e.v != S.v || !k) continue;
+        hipLaunchKernelGGL(k, dim3(S.grid), dim3(S.threads), 0, s, P, ctl);
+        return SBLAS_OK;
     }
-}
-
-template <bool kSys>
-static void launch_trsm_t(const TrsmArgs &P, unsigned *ctl, int grid, hipStream_t s)
-{
-    int c = 1;  // pass width: right-hand sides rounded up to a power of two, <= 64
-    while (c < P.rhs && c < 64) c *= 2;
-    const int v = std::min(trsm_cols_per_lane(c, P.lrow != nullptr), c);
-    const int rp = c / v;
-    if (v == 8) launch_trsm_v<8, kSys>(rp, P, ctl, grid, s);
-    else if (v == 4) launch_trsm_v<4, kSys>(rp, P, ctl, grid, s);
-    else if (v == 2) launch_trsm_v<2, kSys>(rp, P, ctl, grid, s);
-    else launch_trsm_v<1, kSys>(rp, P, ctl, grid, s);
-}
-
-static void launch_trsm(const TrsmArgs &P, unsigned *ctl, int grid, hipStream_t s)
-{
-    if (P.g > 1) launch_trsm_t<true>(P, ctl, grid, s);
-    else launch_trsm_t<false>(P, ctl, grid, s);
+    set_error("sptrsm: no pull kernel for rp %d, v %d, system scope %d", S.rp, S.v, S.sys);
+    return SBLAS_ERR_INVALID;
 }
 
 // ---- SpTRSM push: the reference's dataflow with its lane mappings ---------
@@ -752,19 +732,6 @@ __device__ __forceinline__ void level_row(const int *__restrict__ lrp, const int
     __hip_atomic_store(x + i, (b[i] - sum) / diag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(256) void k_trsv_level(const int *__restrict__ lrp, const int *__restrict__ lcol,
-                                                    const double *__restrict__ lval, const int *__restrict__ lrow,
-                                                    int p0, int p1, int backward, const double *__restrict__ b,
-                                                    double *x)
-{
-    const int k = p0 + (int)(blockIdx.x * 256 + threadIdx.x);
-    if (k < p1) level_row(lrp, lcol, lval, lrow, k, backward, b, x);
-}
-
-constexpr int kLevelWG = 1024;         // threads of the narrow-run workgroup
-constexpr int kLevelNarrow = 2 * kLevelWG;  // a level with <= this many rows is narrow
-constexpr int kLevelMaxWG = 1024;           // grid-barrier workgroups (arrival words)
-
 __global__ __launch_bounds__(kLevelWG) void k_trsv_level_run(
     const int *__restrict__ lrp, const int *__restrict__ lcol, const double *__restrict__ lval,
     const int *__restrict__ lrow, const int *__restrict__ lptr, int l0, int l1, int backward,
@@ -842,40 +809,27 @@ __global__ __launch_bounds__(1024) void k_trsv_level_grid(
     }
 }
 
-// Threads per pull workgroup (one workgroup per CU, grid_for): the waves
-// spinning on a CU.  Every pending lane polls, and the polls share the
-// memory path with the producers' stores and loads, so fewer waves shorten
-// each dependency hop -- as long as enough rows are in flight to cover a
-// level.  Config-5 stand-in (natural order, 985 levels): 1 / 2 / 3 / 4 waves
-// per CU 2.44 / 2.12 / 2.24 / 2.45 ms; level order (a ticket holds 64 rows of
-// one level): 27-point 100^3 1.79 / 1.92 / 1.99 / 2.03 ms, 7-point 0.81 /
-// 0.85 / 0.87 / 0.89 ms (profiles/r05/trsv_waves/).  An experiment build
-// (-DSBLAS_TRSV_THREADS = 64 / 128 / 192 / 256) overrides.  The multi-device blocks keep 256: four
-// blocks sharing one GPU ran 4.7 ms at 4 waves per CU and 6.2 at 2 (each
-// block then has a quarter of the grid), and one block per GPU is unmeasured
-// here.
-#ifndef SBLAS_TRSV_THREADS
-#define SBLAS_TRSV_THREADS 0
-#endif
-static int pull_threads_env()  // fixed when a handle is created
-{
-    constexpr int t = SBLAS_TRSV_THREADS;
-    return t == 64 || t == 128 || t == 192 || t == 256 ? t : 0;
-}
-static int pull_threads(bool level_order, int forced)
-{
-    return forced ? forced : level_order ? 64 : 128;
-}
-
-static int grid_for(int dev)
+// CUs of a device: the ncu of trsv_shape
+static int ncu_of(int dev)
 {
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 1024;
-    // one workgroup per CU (the pull executors' pull_threads() threads each,
-    // the push executor's 256).  More spinning waves is slower: every polling
-    // lane costs an L2 request the producers need (config 5, pull: 1/CU 2.44
-    // ms, 2/CU 2.99 ms, 4/CU 4.92 ms at 256 threads; 8/CU starves the chain).
     return p.multiProcessorCount;
+}
+
+// After the launches of a solve: the control block comes back, and a set
+// abort word (a spin limit ran out somewhere) voids the solve.
+static int finish_solve(unsigned *ctl, hipStream_t s, const char *timeout_msg)
+{
+    SBLAS_HIP(hipGetLastError());
+    unsigned h[kCtlBytes / 4] = {0};
+    SBLAS_HIP(hipMemcpyAsync(h, ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
+    SBLAS_HIP(hipStreamSynchronize(s));
+    if (h[kAbort]) {
+        set_error("%s", timeout_msg);
+        return SBLAS_ERR_HIP;
+    }
+    return SBLAS_OK;
 }
 
 }  // namespace sblas
@@ -897,7 +851,6 @@ int sblas_trsv_create(sblas_trsv *out, int device, int n, int nnz, const int *d_
     T->n = n;
     T->nnz = nnz;
     T->substitution = substitution;
-    T->pull_threads = pull_threads_env();
     auto fail = [&](hipError_t e) {
         set_error("sblas_trsv_create: %s", hipGetErrorString(e));
         sblas_trsv_destroy(T);
@@ -945,34 +898,24 @@ int sblas_trsv_create(sblas_trsv *out, int device, int n, int nnz, const int *d_
 }
 
 // level sets of the solve (rows of level l depend only on levels < l), as
-// findlevel.h:71-147 computes them: level(i) = 1 + max level of i's
-// dependencies, walking columns in solve order
-static void host_levels(const sblas_trsv_s *T, const std::vector<int> &cp, const std::vector<int> &ri,
-                        std::vector<int> &lev, int &nl)
+// findlevel.h:71-147 computes them, from the handle's CSC
+static int download_levels(sblas_trsv_s *T, std::vector<int> &lev)
 {
-    lev.assign((size_t)T->n, 0);
-    nl = 0;
-    for (int k = 0; k < T->n; ++k) {
-        const int i = T->substitution ? T->n - 1 - k : k;
-        const int li = lev[(size_t)i];
-        nl = std::max(nl, li + 1);
-        for (int j = cp[(size_t)i]; j < cp[(size_t)i + 1]; ++j)
-            if (ri[(size_t)j] != i) lev[(size_t)ri[(size_t)j]] = std::max(lev[(size_t)ri[(size_t)j]], li + 1);
-    }
+    std::vector<int> cp((size_t)T->n + 1), ri((size_t)T->nnz);
+    SBLAS_HIP(hipMemcpy(cp.data(), T->colptr, sizeof(int) * cp.size(), hipMemcpyDeviceToHost));
+    if (T->nnz) SBLAS_HIP(hipMemcpy(ri.data(), T->rowidx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost));
+    host_levels(T->n, T->substitution, cp.data(), ri.data(), lev, T->nlevels);
+    return SBLAS_OK;
 }
 
 static int build_levelset(sblas_trsv_s *T, hipStream_t s)
 {
     if (T->lrow) return SBLAS_OK;
     const int n = T->n, nnz = T->nnz;
-    std::vector<int> cp((size_t)n + 1), ri((size_t)nnz);
     SBLAS_HIP(hipStreamSynchronize(s));
-    SBLAS_HIP(hipMemcpy(cp.data(), T->colptr, sizeof(int) * cp.size(), hipMemcpyDeviceToHost));
-    if (nnz) SBLAS_HIP(hipMemcpy(ri.data(), T->rowidx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost));
     std::vector<int> lev;
-    int nl = 0;
-    host_levels(T, cp, ri, lev, nl);
-    T->nlevels = nl;
+    SBLAS_TRY(download_levels(T, lev));
+    const int nl = T->nlevels;
     // counting sort of the rows by level (stable: ascending row in a level)
     T->lptr.assign((size_t)nl + 1, 0);
     for (int i = 0; i < n; ++i) T->lptr[(size_t)lev[(size_t)i] + 1]++;
@@ -997,17 +940,8 @@ static int build_levelset(sblas_trsv_s *T, hipStream_t s)
         lrp[(size_t)k + 1] = lrp[(size_t)k] + len;
     }
     // schedule: maximal runs of narrow levels (one workgroup, workgroup
-    // barriers) and of wide levels (persistent grid, grid barriers), encoded
-    // (l0, l1) narrow / (l0, -l1) wide
-    T->lsched.clear();
-    auto narrow = [&](int l) { return T->lptr[(size_t)l + 1] - T->lptr[(size_t)l] <= kLevelNarrow; };
-    for (int l = 0; l < nl;) {
-        const bool nw = narrow(l);
-        int e = l;
-        while (e < nl && narrow(e) == nw) ++e;
-        T->lsched.push_back({l, nw ? e : -e});
-        l = e;
-    }
+    // barriers) and of wide levels (persistent grid, grid barriers)
+    T->lsched = level_schedule(T->lptr);
     SBLAS_HIP(hipMalloc(&T->lrow, sizeof(int) * lrow.size()));
     SBLAS_HIP(hipMalloc(&T->lrp, sizeof(int) * lrp.size()));
     SBLAS_HIP(hipMalloc(&T->lcol, sizeof(int) * lc.size()));
@@ -1028,39 +962,24 @@ static int solve_levelset(sblas_trsv_s *T, const double *b, double *x, hipStream
     SBLAS_HIP(hipMemsetAsync(T->ctl, 0, kCtlBytes, s));
     int ncu = 0;
     SBLAS_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, T->device));
-#ifndef SBLAS_TRSV_LEVEL_LAUNCH  // experiment builds: one launch per wide level
-#define SBLAS_TRSV_LEVEL_LAUNCH 0
-#endif
-    constexpr int per_level = SBLAS_TRSV_LEVEL_LAUNCH;
-    for (const auto &seg : T->lsched) {
-        if (seg.second < 0 && per_level) {
-            for (int l = seg.first; l < -seg.second; ++l) {
-                const int p0 = T->lptr[(size_t)l], p1 = T->lptr[(size_t)l + 1];
-                hipLaunchKernelGGL(k_trsv_level, dim3((unsigned)((p1 - p0 + 255) / 256)), dim3(256), 0, s, T->lrp,
-                                   T->lcol, T->lval, T->lrow, p0, p1, T->substitution, b, x);
-            }
-        } else if (seg.second < 0) {
-            // one 1024-thread workgroup per CU: all resident (the barrier's premise)
-            const int nwg = std::max(1, std::min(ncu, kLevelMaxWG));
+    TrsvShape S;
+    SBLAS_TRY(trsv_shape(2, 0, 1, false, 1, 1, ncu, &S));
+    for (const TrsvRun &run : T->lsched) {
+        if (run.wide) {
+            // the grid-barrier words start from zero in every wide run
             SBLAS_HIP(hipMemsetAsync(T->ctl, 0, 8, s));
             SBLAS_HIP(hipMemsetAsync(T->larrive, 0, sizeof(unsigned) * kLevelMaxWG, s));
-            hipLaunchKernelGGL(k_trsv_level_grid, dim3((unsigned)nwg), dim3(1024), 0, s, T->lrp, T->lcol, T->lval,
-                               T->lrow, T->lptr_d, seg.first, -seg.second, T->substitution, b, x, T->ctl,
+            hipLaunchKernelGGL(k_trsv_level_grid, dim3((unsigned)S.grid), dim3(S.threads), 0, s, T->lrp, T->lcol,
+                               T->lval, T->lrow, T->lptr_d, run.l0, run.l1, T->substitution, b, x, T->ctl,
                                T->larrive);
         } else {
-            hipLaunchKernelGGL(k_trsv_level_run, dim3(1), dim3(kLevelWG), 0, s, T->lrp, T->lcol, T->lval, T->lrow,
-                               T->lptr_d, seg.first, seg.second, T->substitution, b, x);
+            hipLaunchKernelGGL(k_trsv_level_run, dim3(1), dim3(S.threads), 0, s, T->lrp, T->lcol, T->lval, T->lrow,
+                               T->lptr_d, run.l0, run.l1, T->substitution, b, x);
         }
     }
-    SBLAS_HIP(hipGetLastError());
-    unsigned h[kCtlBytes / 4] = {0};
-    SBLAS_HIP(hipMemcpyAsync(h, T->ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
-    SBLAS_HIP(hipStreamSynchronize(s));
-    if (h[kAbort]) {
-        set_error("sptrsv level-set: grid barrier spin limit exceeded");
-        return SBLAS_ERR_HIP;
-    }
-    return SBLAS_OK;
+    T->last = S;
+    T->solved = true;
+    return finish_solve(T->ctl, s, "sptrsv level-set: grid barrier spin limit exceeded");
 }
 
 // Rows (sampled, <= 65,536 spread over the solve order) with a dependency
@@ -1143,6 +1062,71 @@ int sblas_trsv_pick(sblas_trsv T, void *stream, int *algo)
     return SBLAS_OK;
 }
 
+// The pull executor, SpTRSV (rhs 1) and SpTRSM: tickets in natural order, or
+// in level order (level = true: the rows of a ticket independent)
+static int pull_solve(sblas_trsv_s *T, bool level, int rhs, const double *d_b, double *d_x, hipStream_t s)
+{
+    if (level) SBLAS_TRY(build_levelset(T, s));
+    TrsvShape S;
+    SBLAS_TRY(trsv_shape(level ? 3 : 1, 0, rhs, false, 1, 1, ncu_of(T->device), &S));
+    SBLAS_HIP(hipMemsetAsync(T->ctl, 0, kCtlBytes, s));
+    fill_pending((unsigned long long *)d_x, (long long)T->n * rhs, s);
+    const int *rowptr = level ? T->lrp : T->rrowptr, *col = level ? T->lcol : T->rcol;
+    const double *val = level ? T->lval : T->rval;
+    const int *lrow = level ? T->lrow : nullptr;
+    if (rhs == 1) {
+        auto k = level ? k_trsv_pull<true> : k_trsv_pull<false>;
+        hipLaunchKernelGGL(k, dim3(S.grid), dim3(S.threads), 0, s, rowptr, col, val, T->n, T->substitution, d_b,
+                           (unsigned long long *)d_x, T->ctl, lrow, S.slp);
+    } else {
+        TrsmArgs P{rowptr, col, val, d_b, (unsigned long long *)d_x, nullptr, 1, 0, 0, T->n, T->n, rhs,
+                   T->substitution, 1, lrow, S.slp};
+        SBLAS_TRY(launch_trsm(S, P, T->ctl, s));
+    }
+    T->last = S;
+    T->solved = true;
+    return finish_solve(T->ctl, s,
+                        rhs == 1 ? "sptrsv: spin limit exceeded (matrix not triangular or missing diagonal?)"
+                                 : "sptrsm: spin limit exceeded (matrix not triangular or missing diagonal?)");
+}
+
+// The push executor: k_trsv_push (opt 0, rhs 1) or the SpTRSM's lane mapping opt
+static int push_solve(sblas_trsv_s *T, int opt, int rhs, const double *d_b, double *d_x, hipStream_t s)
+{
+    TrsvShape S;
+    SBLAS_TRY(trsv_shape(0, opt, rhs, false, 1, 1, ncu_of(T->device), &S));
+    double *left = T->left;
+    if (opt != 0) {
+        const size_t need = (size_t)T->n * rhs;
+        if (need > T->left_rhs_cap) {
+            if (T->left_rhs) SBLAS_HIP(hipFree(T->left_rhs));
+            T->left_rhs = nullptr;
+            T->left_rhs_cap = 0;
+            SBLAS_HIP(hipMalloc(&T->left_rhs, sizeof(double) * need));
+            T->left_rhs_cap = need;
+        }
+        left = T->left_rhs;
+    }
+    SBLAS_HIP(hipMemsetAsync(T->ctl, 0, kCtlBytes, s));
+    SBLAS_HIP(hipMemsetAsync(T->done, 0, sizeof(int) * T->n, s));
+    SBLAS_HIP(hipMemsetAsync(left, 0, sizeof(double) * T->n * rhs, s));
+#define SBLAS_TRSM_PUSH(O)                                                                                       \
+    hipLaunchKernelGGL(k_trsm_push<O>, dim3(S.grid), dim3(S.threads), 0, s, T->colptr, T->rowidx, T->val,       \
+                       T->in_degree, T->n, T->substitution, rhs, d_b, d_x, T->done, left, T->ctl)
+    if (opt == 0)
+        hipLaunchKernelGGL(k_trsv_push, dim3(S.grid), dim3(S.threads), 0, s, T->colptr, T->rowidx, T->val,
+                           T->in_degree, T->n, T->substitution, d_b, d_x, T->done, left, T->ctl);
+    else if (opt == kOptNnz) SBLAS_TRSM_PUSH(kOptNnz);
+    else if (opt == kOptRhs) SBLAS_TRSM_PUSH(kOptRhs);
+    else SBLAS_TRSM_PUSH(kOptAuto);
+#undef SBLAS_TRSM_PUSH
+    T->last = S;
+    T->solved = true;
+    return finish_solve(T->ctl, s,
+                        opt == 0 ? "sptrsv: spin limit exceeded (matrix not triangular or missing diagonal?)"
+                                 : "sptrsm: spin limit exceeded (matrix not triangular or missing diagonal?)");
+}
+
 int sblas_trsv_solve(sblas_trsv T, int algo, const double *d_b, double *d_x, void *stream)
 {
     if (!T || !d_b || !d_x || algo < 0 || algo > 4) return SBLAS_ERR_INVALID;
@@ -1155,67 +1139,8 @@ int sblas_trsv_solve(sblas_trsv T, int algo, const double *d_b, double *d_x, voi
         algo = a;
     }
     if (algo == 2) return solve_levelset(T, d_b, d_x, s);
-    if (algo == 3) SBLAS_TRY(build_levelset(T, s));
-    SBLAS_HIP(hipMemsetAsync(T->ctl, 0, kCtlBytes, s));
-    const int grid = grid_for(T->device);
-    // poll back-off of the pull executors (k_trsv_pull header): natural order
-    // one s_sleep(1) per poll; level order the adaptive back-off up to 64
-    // units (-6: 27-point 100^3 2.25 -> 2.03 ms, 7-point 0.97 -> 0.88 ms; -8
-    // and deeper lose; profiles/r03/sptrsv_sleep/)
-    const int slp = algo == 3 ? -6 : 1;
-    const int pth = pull_threads(algo == 3, T->pull_threads);
-    if (algo == 3) {  // sync-free pull, tickets in level order
-        fill_pending((unsigned long long *)d_x, T->n, s);
-        hipLaunchKernelGGL(k_trsv_pull<true>, dim3(grid), dim3(pth), 0, s, T->lrp, T->lcol, T->lval, T->n,
-                           T->substitution, d_b, (unsigned long long *)d_x, T->ctl, T->lrow, slp);
-    } else if (algo == 0) {
-        SBLAS_HIP(hipMemsetAsync(T->done, 0, sizeof(int) * T->n, s));
-        SBLAS_HIP(hipMemsetAsync(T->left, 0, sizeof(double) * T->n, s));
-        hipLaunchKernelGGL(k_trsv_push, dim3(grid), dim3(256), 0, s, T->colptr, T->rowidx, T->val,
-                           T->in_degree, T->n, T->substitution, d_b, d_x, T->done, T->left, T->ctl);
-    } else {
-        fill_pending((unsigned long long *)d_x, T->n, s);
-        hipLaunchKernelGGL(k_trsv_pull<false>, dim3(grid), dim3(pth), 0, s, T->rrowptr, T->rcol, T->rval,
-                           T->n, T->substitution, d_b, (unsigned long long *)d_x, T->ctl, nullptr, slp);
-    }
-    SBLAS_HIP(hipGetLastError());
-    unsigned h[kCtlBytes / 4] = {0};
-    SBLAS_HIP(hipMemcpyAsync(h, T->ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
-    SBLAS_HIP(hipStreamSynchronize(s));
-    if (h[kAbort]) {
-        set_error("sptrsv: spin limit exceeded (matrix not triangular or missing diagonal?)");
-        return SBLAS_ERR_HIP;
-    }
-    return SBLAS_OK;
-}
-
-// SpTRSM pull: tickets in natural order, or in level order (level = true:
-// the rows of a ticket independent, as algo 3 of sblas_trsv_solve)
-static int trsm_pull(sblas_trsv_s *T, bool level, int rhs, const double *d_b, double *d_x, hipStream_t s)
-{
-    if (level) SBLAS_TRY(build_levelset(T, s));
-    SBLAS_HIP(hipMemsetAsync(T->ctl, 0, kCtlBytes, s));
-    fill_pending((unsigned long long *)d_x, (long long)T->n * rhs, s);
-    TrsmArgs P{level ? T->lrp : T->rrowptr, level ? T->lcol : T->rcol, level ? T->lval : T->rval, d_b,
-               (unsigned long long *)d_x, nullptr, 1, 0, 0, T->n, T->n, rhs, T->substitution, 1,
-               level ? T->lrow : nullptr, level ? -6 : 1};
-    // workgroups per CU (x grid_for's): natural order at rhs >= 16 gains from
-    // more rows in flight (config 5: rhs 16 / 32 / 64 at 1 -> 2 -> 4 per CU:
-    // 6.50 / 10.2 / 16.1 -> 4.63 / 8.55 / 10.4 -> 4.86 / 8.53 / 9.26 ms); level
-    // order loses (27-point stencil rhs 64: 4.93 / 5.12 / 5.32 ms;
-    // profiles/r03/sptrsm/trsm_grid2/).
-    const int mult = level || rhs < 16 ? 1 : rhs <= 32 ? 2 : 4;
-    const int grid = grid_for(T->device) * mult;
-    launch_trsm(P, T->ctl, grid, s);
-    SBLAS_HIP(hipGetLastError());
-    unsigned h[kCtlBytes / 4] = {0};
-    SBLAS_HIP(hipMemcpyAsync(h, T->ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
-    SBLAS_HIP(hipStreamSynchronize(s));
-    if (h[kAbort]) {
-        set_error("sptrsm: spin limit exceeded (matrix not triangular or missing diagonal?)");
-        return SBLAS_ERR_HIP;
-    }
-    return SBLAS_OK;
+    if (algo == 0) return push_solve(T, 0, 1, d_b, d_x, s);
+    return pull_solve(T, algo == 3, 1, d_b, d_x, s);
 }
 
 int sblas_trsv_solve_rhs(sblas_trsv T, int rhs, const double *d_b, double *d_x, void *stream)
@@ -1224,7 +1149,7 @@ int sblas_trsv_solve_rhs(sblas_trsv T, int rhs, const double *d_b, double *d_x, 
     if (rhs == 1) return sblas_trsv_solve(T, 1, d_b, d_x, stream);
     if (T->n == 0) return SBLAS_OK;
     DeviceGuard g(T->device);
-    return trsm_pull(T, false, rhs, d_b, d_x, (hipStream_t)stream);
+    return pull_solve(T, false, rhs, d_b, d_x, (hipStream_t)stream);
 }
 
 int sblas_trsv_solve_rhs_opt(sblas_trsv T, int algo, int opt, int rhs, const double *d_b,
@@ -1242,35 +1167,18 @@ int sblas_trsv_solve_rhs_opt(sblas_trsv T, int algo, int opt, int rhs, const dou
         if (a < 0) return -a;
         algo = a;
     }
-    if (algo != 0) return trsm_pull(T, algo == 3, rhs, d_b, d_x, s);
-    const size_t need = (size_t)T->n * rhs;
-    if (need > T->left_rhs_cap) {
-        if (T->left_rhs) SBLAS_HIP(hipFree(T->left_rhs));
-        T->left_rhs = nullptr;
-        T->left_rhs_cap = 0;
-        SBLAS_HIP(hipMalloc(&T->left_rhs, sizeof(double) * need));
-        T->left_rhs_cap = need;
-    }
-    SBLAS_HIP(hipMemsetAsync(T->ctl, 0, kCtlBytes, s));
-    SBLAS_HIP(hipMemsetAsync(T->done, 0, sizeof(int) * T->n, s));
-    SBLAS_HIP(hipMemsetAsync(T->left_rhs, 0, sizeof(double) * need, s));
-    const int grid = grid_for(T->device);
-#define SBLAS_TRSM_PUSH(O)                                                                        \
-    hipLaunchKernelGGL(k_trsm_push<O>, dim3(grid), dim3(256), 0, s, T->colptr, T->rowidx, T->val, \
-                       T->in_degree, T->n, T->substitution, rhs, d_b, d_x, T->done, T->left_rhs,  \
-                       T->ctl)
-    if (opt == kOptNnz) SBLAS_TRSM_PUSH(kOptNnz);
-    else if (opt == kOptRhs) SBLAS_TRSM_PUSH(kOptRhs);
-    else SBLAS_TRSM_PUSH(kOptAuto);
-#undef SBLAS_TRSM_PUSH
-    SBLAS_HIP(hipGetLastError());
-    unsigned h[kCtlBytes / 4] = {0};
-    SBLAS_HIP(hipMemcpyAsync(h, T->ctl, kCtlBytes, hipMemcpyDeviceToHost, s));
-    SBLAS_HIP(hipStreamSynchronize(s));
-    if (h[kAbort]) {
-        set_error("sptrsm: spin limit exceeded (matrix not triangular or missing diagonal?)");
-        return SBLAS_ERR_HIP;
-    }
+    if (algo != 0) return pull_solve(T, algo == 3, rhs, d_b, d_x, s);
+    return push_solve(T, opt, rhs, d_b, d_x, s);
+}
+
+int sblas_trsv_info(sblas_trsv T, long long *info)
+{
+    if (!T || !info || !T->solved) return SBLAS_ERR_INVALID;
+    trsv_shape_info(T->last, info);
+    // the level-set executor's narrow and wide runs
+    info[kTrsvShapeFields] = info[kTrsvShapeFields + 1] = 0;
+    if (T->last.executor == kTrsvLevelSet)
+        for (const TrsvRun &run : T->lsched) info[kTrsvShapeFields + (run.wide ? 1 : 0)]++;
     return SBLAS_OK;
 }
 
@@ -1279,13 +1187,8 @@ int sblas_trsv_levels(sblas_trsv T, int *nlevel)
     if (!T || !nlevel) return SBLAS_ERR_INVALID;
     if (T->nlevels < 0) {
         DeviceGuard g(T->device);
-        std::vector<int> cp((size_t)T->n + 1), ri((size_t)T->nnz);
-        SBLAS_HIP(hipMemcpy(cp.data(), T->colptr, sizeof(int) * cp.size(), hipMemcpyDeviceToHost));
-        if (T->nnz) SBLAS_HIP(hipMemcpy(ri.data(), T->rowidx, sizeof(int) * ri.size(), hipMemcpyDeviceToHost));
         std::vector<int> lev;
-        int nl = 0;
-        host_levels(T, cp, ri, lev, nl);
-        T->nlevels = nl;
+        SBLAS_TRY(download_levels(T, lev));
     }
     *nlevel = T->nlevels;
     return SBLAS_OK;
@@ -1334,12 +1237,10 @@ namespace {
 // floor(d*m/(np*task)), sptrsv_v3/src/sptrsv_syncfree_cuda.h:276-300).
 // Every block has its own stream and all are launched before any is waited
 // for, so blocks that share a GPU run CONCURRENTLY like blocks on different
-// GPUs: each gets grid_for(dev) / (blocks on dev) workgroups, so the blocks
+// GPUs: each gets (CUs of dev) / (blocks on dev) workgroups, so the blocks
 // of one device are co-resident.  Launches go in block order; a block only
 // waits for lower blocks, which were enqueued first on every hardware queue,
-// so streams sharing a queue cannot deadlock.  An experiment build with
-// -DSBLAS_TRSV_MGPU_SERIAL=1 runs
-// the blocks of one device in order on one stream instead (A/B timing).
+// so streams sharing a queue cannot deadlock.
 struct TrsvMgpuDev {
     int phys = 0;
     int nloc = 0;
@@ -1355,14 +1256,15 @@ struct TrsvMgpuDev {
 
 struct sblas_trsv_mgpu_s {
     int n = 0, rhs = 1, nblocks = 0, ndev = 0;
-    bool bwd = false, serial = false;
-    int pull_threads = 0;  // fixed at create (0: 256 threads per workgroup)
+    bool bwd = false;
     std::vector<int> ob;                  // block boundaries in the solve order
     std::vector<TrsvMgpuDev> D;
-    std::vector<hipStream_t> streams;     // per block (serial: per device's first block)
-    std::vector<int> on_phys, first_on;
+    std::vector<hipStream_t> streams;     // per block
+    std::vector<int> on_phys;             // blocks per device
     std::vector<std::pair<int, int>> peers;  // peer links taken (peer_acquire), released on destroy
-    hipStream_t stream_of(int d) const { return streams[serial ? first_on[D[d].phys] : d]; }
+    // block 0's shape in the last run (sblas_trsv_mgpu_shape)
+    bool solved = false;
+    sblas::TrsvShape last{};
 };
 
 namespace {
@@ -1407,11 +1309,6 @@ int trsv_mgpu_build(sblas_trsv_mgpu_s *H, const int *colptr, const int *rowidx, 
     H->rhs = rhs;
     H->nblocks = nblocks;
     H->ndev = ndev;
-#ifndef SBLAS_TRSV_MGPU_SERIAL  // experiment builds: one device's blocks in order on one stream
-#define SBLAS_TRSV_MGPU_SERIAL 0
-#endif
-    H->serial = SBLAS_TRSV_MGPU_SERIAL != 0;
-    H->pull_threads = pull_threads_env();
     const int nnz = colptr[n];
     const bool bwd = H->bwd = substitution == 1;
     // CSC of L == CSR of L^T; stable transpose gives CSR of L with columns
@@ -1449,16 +1346,12 @@ int trsv_mgpu_build(sblas_trsv_mgpu_s *H, const int *colptr, const int *rowidx, 
     H->D.assign(ngpu, TrsvMgpuDev{});
     H->streams.assign(ngpu, nullptr);
     H->on_phys.assign(count, 0);
-    H->first_on.assign(count, -1);
     const int nphys = std::min(count, ndev);
     for (int d = 0; d < ngpu; ++d) {
         H->D[d].phys = (d % ndev) % count;
         H->on_phys[H->D[d].phys]++;
-        if (H->first_on[H->D[d].phys] < 0) H->first_on[H->D[d].phys] = d;
     }
     for (int d = 0; d < ngpu; ++d) {
-        // serial mode: the blocks of one device share its first block's stream
-        if (H->serial && H->first_on[H->D[d].phys] != d) continue;
         DeviceGuard g(H->D[d].phys);
         MG(hipStreamCreateWithFlags(&H->streams[d], hipStreamNonBlocking));
     }
@@ -1525,7 +1418,7 @@ int trsv_mgpu_run(sblas_trsv_mgpu_s *H, const double *b, double *x, double *solv
     for (int d = 0; d < ngpu; ++d) {
         TrsvMgpuDev &q = H->D[d];
         DeviceGuard g(q.phys);
-        hipStream_t s = H->stream_of(d);
+        hipStream_t s = H->streams[d];
         for (int t = 0; t < q.nloc; ++t) {
             const int i = row_of(ob[d] + t);
             for (int k = 0; k < rhs; ++k) q.hb[(size_t)t * rhs + k] = b[(size_t)i * rhs + k];
@@ -1537,29 +1430,32 @@ int trsv_mgpu_run(sblas_trsv_mgpu_s *H, const double *b, double *x, double *solv
     }
     for (int d = 0; d < ngpu; ++d) {
         DeviceGuard g(H->D[d].phys);
-        MG(hipStreamSynchronize(H->stream_of(d)));
+        MG(hipStreamSynchronize(H->streams[d]));
     }
     const double t0 = sblas_get_time();
     for (int d = 0; d < ngpu; ++d) {
         TrsvMgpuDev &q = H->D[d];
         DeviceGuard g(q.phys);
         const int nloc = q.nloc;
-        // co-resident blocks: the device's workgroup budget split between them
-        const int grid = H->serial ? grid_for(q.phys) : std::max(1, grid_for(q.phys) / H->on_phys[q.phys]);
-        if (nloc > 0 && rhs == 1) {
+        TrsvShape S;
+        SBLAS_TRY(trsv_shape(1, 0, rhs, true, ngpu, H->on_phys[q.phys], ncu_of(q.phys), &S));
+        if (d == 0) {
+            H->last = S;
+            H->solved = true;
+        }
+        if (nloc > 0 && rhs == 1) {  // polls at system scope with one s_sleep(1) per poll: S.sys, S.slp
             TrsvPart P{q.rowptr, q.col, q.val, q.b, q.xs, ngpu, d, ob[d], nloc, n, bwd ? 1 : 0};
-            hipLaunchKernelGGL(k_trsv_pull_part, dim3(grid), dim3(H->pull_threads ? H->pull_threads : 256), 0, H->stream_of(d), P,
-                               q.ctl);
+            hipLaunchKernelGGL(k_trsv_pull_part, dim3(S.grid), dim3(S.threads), 0, H->streams[d], P, q.ctl);
         } else if (nloc > 0) {
             TrsmArgs P{q.rowptr, q.col, q.val, q.b,    q.x, q.xs, ngpu, d, ob[d], nloc, n, rhs, bwd ? 1 : 0, 0,
-                       nullptr, 1};
-            launch_trsm(P, q.ctl, grid, H->stream_of(d));
+                       nullptr, S.slp};
+            SBLAS_TRY(launch_trsm(S, P, q.ctl, H->streams[d]));
         }
         MG(hipGetLastError());
     }
     for (int d = 0; d < ngpu; ++d) {
         DeviceGuard g(H->D[d].phys);
-        MG(hipStreamSynchronize(H->stream_of(d)));
+        MG(hipStreamSynchronize(H->streams[d]));
     }
     if (solve_ms) *solve_ms = (sblas_get_time() - t0) * 1e3;
     for (int d = 0; d < ngpu; ++d) {
@@ -1648,6 +1544,13 @@ int sblas_trsv_mgpu_info(sblas_trsv_mgpu H, int *nblocks, int *block_device, int
         if (block_device) block_device[d] = H->D[d].phys;
         if (block_rows) block_rows[d] = H->D[d].nloc;
     }
+    return SBLAS_OK;
+}
+
+int sblas_trsv_mgpu_shape(sblas_trsv_mgpu H, long long *info)
+{
+    if (!H || !info || !H->solved) return SBLAS_ERR_INVALID;
+    trsv_shape_info(H->last, info);
     return SBLAS_OK;
 }
 

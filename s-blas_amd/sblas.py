@@ -121,6 +121,10 @@ _sig("sblas_csr_set_deterministic", _i, _p, _i)
 _sig("sblas_csr_xsort_info", _i, _p, _p)
 _sig("sblas_xsort_plan_host", _i, _i, _i, _p, _i, _p, _i, _i, _p, _p, _ll, _p, _ll)
 _sig("sblas_transpose_shape_host", _i, _i, _i, _ll, _i, _p)
+_sig("sblas_trsv_shape_host", _i, _i, _i, _i, _i, _i, _i, _i, _p)
+_sig("sblas_trsv_levels_host", _i, _i, _p, _p, _i, _p)
+_sig("sblas_trsv_info", _i, _p, _p)
+_sig("sblas_trsv_mgpu_shape", _i, _p, _p)
 _sig("sblas_spmm_shape_host", _i, _i, _i, _p, _p, _i, _i, _ll, _i, C.c_ulonglong, _d, _p)
 _sig("sblas_spmm_info", _i, _p, _p)
 _sig("sblas_csr_get_deterministic", _i, _p, _p)
@@ -271,6 +275,29 @@ def transpose_shape_host(m: int, n: int, nnz: int, ncu: int) -> dict:
     keys = ("msd", "c", "bA", "bB", "passes", "rb", "ntiles", "S", "nwg", "JB", "nwgB", "packA", "pack", "nbC",
             "ftile", "lean", "fgrid", "ncnt")
     return {k: int(v) for k, v in zip(keys, info)}
+
+
+TRSV_SHAPE_KEYS = ("executor", "level_order", "c", "rp", "v", "passes", "rows_per_claim", "sys", "threads", "grid",
+                   "slp")
+
+
+def trsv_shape_host(algo: int, opt: int, rhs: int, mgpu: bool, blocks: int, blocks_on_device: int, ncu: int) -> dict:
+    """What a triangular solve decides before its launch (sblas_trsv_shape_host;
+    no GPU): TRSV_SHAPE_KEYS.  executor 0 push, 1 pull, 2 level-set."""
+    info = np.zeros(len(TRSV_SHAPE_KEYS), np.int64)
+    check(lib.sblas_trsv_shape_host(algo, opt, rhs, int(mgpu), blocks, blocks_on_device, ncu, ptr(info)),
+          "trsv_shape_host")
+    return {k: int(v) for k, v in zip(TRSV_SHAPE_KEYS, info)}
+
+
+def trsv_levels_host(colptr, rowidx, substitution: int = 0) -> dict:
+    """Level analysis of a host CSC triangle (sblas_trsv_levels_host; no GPU):
+    levels, widest (rows of the widest level), narrow_runs, wide_runs."""
+    cp = np.ascontiguousarray(colptr, np.int32)
+    ri = np.ascontiguousarray(rowidx, np.int32)
+    info = np.zeros(4, np.int64)
+    check(lib.sblas_trsv_levels_host(len(cp) - 1, ptr(cp), ptr(ri), substitution, ptr(info)), "trsv_levels_host")
+    return {k: int(v) for k, v in zip(("levels", "widest", "narrow_runs", "wide_runs"), info)}
 
 
 SPMM_SHAPE_KEYS = ("nmfma", "nsparse", "sparse_nnz", "rowform", "ctile", "ct_supported", "ns", "nrb", "R", "rbits",
@@ -438,6 +465,12 @@ class TrsvMgpu:
         rw = np.zeros(nb.value, np.int32)
         check(lib.sblas_trsv_mgpu_info(self.h, None, ptr(dv), ptr(rw)), "trsv_mgpu_info")
         return [(int(d), int(r)) for d, r in zip(dv, rw)]
+
+    def shape(self) -> dict:
+        """Block 0's shape in the last run (sblas_trsv_mgpu_shape): TRSV_SHAPE_KEYS."""
+        info = np.zeros(len(TRSV_SHAPE_KEYS), np.int64)
+        check(lib.sblas_trsv_mgpu_shape(self.h, ptr(info)), "trsv_mgpu_shape")
+        return {k: int(v) for k, v in zip(TRSV_SHAPE_KEYS, info)}
 
     def close(self):
         if self.h:
@@ -828,6 +861,13 @@ class DeviceTRSV:
         n = C.c_int()
         check(lib.sblas_trsv_levels(self.h, C.byref(n)), "trsv_levels")
         return n.value
+
+    def info(self) -> dict:
+        """The shape of the last solve (sblas_trsv_info): TRSV_SHAPE_KEYS, then
+        narrow_runs and wide_runs of the level-set executor's schedule."""
+        info = np.zeros(len(TRSV_SHAPE_KEYS) + 2, np.int64)
+        check(lib.sblas_trsv_info(self.h, ptr(info)), "trsv_info")
+        return {k: int(v) for k, v in zip(TRSV_SHAPE_KEYS + ("narrow_runs", "wide_runs"), info)}
 
     def close(self) -> None:
         if self.h:

@@ -7,6 +7,7 @@ import pytest
 from conftest import GOLDEN
 from spmm_cases import FORM_KERNELS, FORM_OPTS, block_dense_csr, spmm_bound, spmm_matrix
 from transpose_cases import CASES, EDGES, MGPU_CASES, rand_csr, transpose_case, transpose_edge
+from trsv_cases import _banded_system, csc_matmat, schedule_system
 
 pytestmark = pytest.mark.gpu
 
@@ -321,33 +322,15 @@ def test_sptrsv_random_wellconditioned(torch_cuda, sb, orc, algo):
 @pytest.mark.parametrize("shape", ["chain", "wide"])
 def test_sptrsv_levelset_schedule(torch_cuda, sb, orc, sub, shape):
     """Level-set executor over both schedule kinds: "chain" = a bidiagonal
-    system (n levels of one row: one narrow run in one workgroup), "wide" = a
-    diagonal-heavy system with a few long dependency columns (levels of more
-    than 2,048 rows: one grid launch per level), forward and backward; exact
+    system (n levels of one row: one narrow run, one workgroup with a
+    workgroup barrier per level), "wide" = a diagonal-heavy system with a few
+    long dependency columns (its first four levels have more than 2,048 rows:
+    one wide run, a persistent grid of one workgroup per CU with a grid
+    barrier per level, then one narrow run), forward and backward; exact
     integer KATs (x integer, values small integers)."""
     torch = torch_cuda
-    rng = np.random.default_rng(17 + sub)
-    n = 5000 if shape == "chain" else 60000
-    cols, rows = [], []
-    for c in range(n):
-        deps = []
-        if shape == "chain":
-            if (sub == 0 and c + 1 < n) or (sub == 1 and c > 0):
-                deps = [c + 1 if sub == 0 else c - 1]
-        else:
-            lo, hi = (c + 1, min(n, c + 4000)) if sub == 0 else (max(0, c - 4000), c)
-            if hi > lo and rng.random() < 0.3:
-                deps = sorted(set(rng.integers(lo, hi, 2).tolist()))
-        rr = [c] + deps if sub == 0 else deps + [c]
-        rows.append(rr)
-    cp = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
-    ri = np.concatenate(rows).astype(np.int32)
-    cv = rng.integers(1, 4, len(ri)).astype(np.float64)
-    diag_pos = cp[:-1] if sub == 0 else cp[1:] - 1
-    cv[diag_pos] = 1.0
-    xref = rng.integers(-3, 4, n).astype(np.float64)
-    colidx = np.repeat(np.arange(n), np.diff(cp))
-    b = np.bincount(ri, weights=cv * xref[colidx], minlength=n)
+    cp, ri, cv, b, xref = schedule_system(shape, sub)
+    n = len(cp) - 1
     d = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (cp, ri, cv, b)]
     T = sb.DeviceTRSV(0, n, len(ri), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), sub)
     xd = torch.zeros(n, dtype=torch.float64, device="cuda")
@@ -356,6 +339,9 @@ def test_sptrsv_levelset_schedule(torch_cuda, sb, orc, sub, shape):
         T.solve(2, d[3].data_ptr(), xd.data_ptr())
         torch.cuda.synchronize()
         assert np.array_equal(xd.cpu().numpy(), xref)
+        info = T.info()
+        assert (info["executor"], info["threads"]) == (2, 1024)
+        assert (info["narrow_runs"], info["wide_runs"]) == ((1, 0) if shape == "chain" else (1, 1))
     if shape == "chain":
         assert T.levels() == n
     T.close()
@@ -409,14 +395,6 @@ def test_sptrsv_mgpu_banded_matches_single(torch_cuda, sb, ngpu):
     x, _ = sb.trsv_mgpu_solve(cp, ri, v, n, b, ngpu, 0)
     assert np.array_equal(x, want)
     assert np.abs(x - xref).sum() / np.abs(xref).sum() < 1e-10
-
-
-def _banded_system(sb, n, seed=11):
-    cp, ri, v = sb.gen_lower_banded(n, 4, 5000, seed)
-    xref = np.floor(sb.gen_vector(n, seed + 1) * 10.0) + 1.0
-    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(cp))
-    b = np.bincount(ri, weights=v * xref[cols], minlength=n)
-    return cp, ri, v, b, xref
 
 
 @pytest.mark.parametrize("blocks,rhs,sub", [(1, 1, 0), (4, 1, 0), (3, 1, 1), (4, 3, 0), (2, 5, 1)])
@@ -487,15 +465,6 @@ def test_sptrsv_reference_api_mgpu(torch_cuda, sb, capfd):
                                       3, sb.ptr(x), sb.ptr(b), sb.ptr(xref), sb.ptr(gf), 3)
     assert rc == 0 and np.array_equal(x, xref)
     assert "executor passed!" in capfd.readouterr().out
-
-
-def csc_matmat(cp, ri, cv, X):
-    """B = L X for CSC L (exact for the integer KAT systems)."""
-    B = np.zeros_like(X)
-    for c in range(len(cp) - 1):
-        s, e = cp[c], cp[c + 1]
-        B[ri[s:e]] += cv[s:e, None] * X[c][None, :]
-    return B
 
 
 @pytest.mark.parametrize("name", ["qh768", "ash85"])
