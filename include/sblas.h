@@ -206,7 +206,10 @@ int sblas_xsort_plan_host(int m, int n, const long long *rowptr, int resident, c
  * must be comparable).  what: 0 = the chunk storage (keys and values, chunks
  * x 3072 B), 1 = the item records, 2 = the wide ranges' records, 3 = the 32
  * initial claim heads (as the build armed them; launches advance and re-arm
- * the resident ones).  *bytes receives the buffer's size; host_buf == NULL
+ * the resident ones), 4 = the value map of sblas_csr_set_values (256 int32 per
+ * chunk in the chunk's own value order: the slot's index into the CSR values,
+ * -1 for padding; SBLAS_ERR_INVALID until a sblas_csr_set_values call has built
+ * it).  *bytes receives the buffer's size; host_buf == NULL
  * only sizes; cap_bytes below the size is SBLAS_ERR_INVALID.  Waits for the
  * device. */
 int sblas_csr_xsort_export(sblas_csr A, int what, void *host_buf, long long cap_bytes, long long *bytes);
@@ -234,6 +237,34 @@ int sblas_csr_panels(sblas_csr A, int algo, int *panels);
 long long sblas_csr_plan_bytes(sblas_csr A, int algo);
 /* bytes the algorithm must move per call (DESIGN.md "Algorithmic bytes"). */
 long long sblas_spmv_algorithmic_bytes(sblas_csr A, int beta_nonzero);
+/* Replace the values of the handle's entries; pattern, plans, AUTO's choice and
+ * deterministic mode are kept.  d_val: DEVICE, nnz doubles in the order of the
+ * arrays the handle was made from (upload_slice: elements idx_begin..idx_end).
+ * Must not alias the handle's storage.
+ * After the call the CSR values and every value buffer of every analysed SpMV
+ * plan hold the bytes a fresh handle made from the same pattern with d_val and
+ * analysed the same way holds; index, descriptor and partial buffers are not
+ * touched.  Each plan that copies values (XSORT's chunk storage, the XCD-panel
+ * CSR of PANEL and of ROWSPLIT's panel form, CSR5's panel tiles) keeps a map
+ * of 4 B per value slot, built by the first call after the plan's analysis
+ * (that call waits for the device, as an analysis does) and kept with the
+ * plan; from then on a call is one copy of d_val and one gather pass per
+ * resident layout, stream-ordered with the handle's sblas_spmv launches on
+ * `stream` under the same rule of one launch in flight: no sort, no planner,
+ * no allocation, no wait.  If a map cannot be allocated that plan is freed
+ * and rebuilt from the new values (sblas_csr_values_info says so).
+ * An SpMM plan merges duplicate entries into its fragments and is dropped:
+ * the next sblas_spmm rebuilds it from the new values, tuned to that call's
+ * width, and sblas_spmm_info is SBLAS_ERR_INVALID until then, as before a
+ * first call.  sblas_csr_transpose reads the CSR values and needs nothing.
+ * A null handle, or a null d_val with nnz > 0, is SBLAS_ERR_INVALID; nnz == 0
+ * is SBLAS_OK. */
+int sblas_csr_set_values(sblas_csr A, const double *d_val, void *stream);
+/* info[6]: set_values calls so far; bitmask of algorithms whose plan holds a
+ * value map (bit SBLAS_SPMV_x); resident map bytes; wall seconds of the last
+ * map build; 1.0 if the last call fell back to rebuilding a plan; 1.0 if it
+ * dropped an SpMM plan */
+int sblas_csr_values_info(sblas_csr A, double *info);
 
 /* SpMM on a device handle: C(m x n, ldc) = alpha*A*B(k x n, ldb) + beta*C.
  * b_layout 0 = column-major B (ld=ldb >= k), 1 = row-major B (ld >= n).
@@ -512,6 +543,15 @@ int sblas_ctx_matrix_upload_parts(sblas_ctx ctx, int m, int n, const long long *
                                   const int *col, const double *val, int algo, int parts);
 /* The parts the loaded matrix runs in (1: not overlapped; 0: nothing loaded). */
 int sblas_ctx_parts(sblas_ctx ctx, int *parts);
+/* New values for the loaded matrix: host val of the global CSR given to
+ * sblas_ctx_matrix_upload*.  Every device slice (and part handle) gets its
+ * share through sblas_csr_set_values; partition, plans and exchange are kept.
+ * The upload recorded each device's global element ranges (one under
+ * partitions 1 and 2, one per local chunk under the cyclic partition), so
+ * neither rowptr nor col is needed.  The shares are staged in pinned memory
+ * and copied on each device's main stream; the call returns once they have
+ * been consumed.  SBLAS_ERR_INVALID when nothing is loaded. */
+int sblas_ctx_matrix_set_values(sblas_ctx ctx, const double *val);
 /* Device d's share: rows, entries, and the algorithmic bytes of its SpMV
  * launch with beta != 0 (sblas_spmv_algorithmic_bytes).  Any may be NULL. */
 int sblas_ctx_slice_info(sblas_ctx ctx, int d, long long *rows, long long *nnz,

@@ -420,7 +420,7 @@ int sblas_csr_xsort_info(sblas_csr A, long long *info)
 
 int sblas_csr_xsort_export(sblas_csr A, int what, void *host_buf, long long cap_bytes, long long *bytes)
 {
-    if (!A || !bytes || what < 0 || what > 3) return SBLAS_ERR_INVALID;
+    if (!A || !bytes || what < 0 || what > 4) return SBLAS_ERR_INVALID;
     const XsPlan &P = A->xs;
     if (!P.ready) {
         set_error("sblas_csr_xsort_export: no analysed XSORT plan");
@@ -434,6 +434,14 @@ int sblas_csr_xsort_export(sblas_csr A, int what, void *host_buf, long long cap_
     case 0: src = P.key; nb = P.nchunks * 3072LL; break;
     case 1: src = P.xrec; nb = P.xrec_bytes; break;
     case 2: src = P.wranges; nb = (long long)sizeof(XsRange) * P.nwide; break;
+    case 4:  // the value map of sblas_csr_set_values (values.hip), once a call has built it
+        if (!P.vmap) {
+            set_error("sblas_csr_xsort_export: no value map (sblas_csr_set_values builds it)");
+            return SBLAS_ERR_INVALID;
+        }
+        src = P.vmap;
+        nb = P.nchunks * (long long)(kXsChunk * sizeof(int));
+        break;
     default:  // as the build armed them: both parities start past the static items
         for (int k = 0; k < 32; ++k) heads[k] = (k & 15) < 8 ? P.qstat[k & 15] : 0;
         nb = (long long)sizeof(heads);

@@ -26,6 +26,7 @@
 #include <rccl/rccl.h>
 
 #include "sblas_internal.hpp"
+#include "value_ranges.hpp"
 
 struct sblas_ctx_s {
     int g = 0;
@@ -67,6 +68,12 @@ struct sblas_ctx_s {
     std::vector<hipEvent_t> evc;       // [g] comm stream done (joins the main stream)
     std::vector<int> palgo;            // [g] the algorithm the part handles run (AUTO resolved)
     int parts_req = 1;                 // requested by sblas_ctx_matrix_upload_parts
+    // sblas_ctx_matrix_set_values: the global element ranges each device's
+    // slice was made from (one per local chunk under the cyclic partition,
+    // else one), and the elements of each part handle (their ranges follow
+    // one another in the device's)
+    std::vector<std::vector<sblas::ValRange>> vr;  // [g]
+    std::vector<long long> pcount;                 // [g * parts]
     // one device, one part: nothing to exchange; yfull[0] IS ylocal[0] (its
     // first m rows are y in row order under either partition)
     bool yalias = false;
@@ -379,6 +386,7 @@ void free_parts(sblas_ctx_s &C)
     }
     C.P.clear();
     C.plo.clear();
+    C.pcount.clear();
     C.parts = 1;
 }
 
@@ -397,6 +405,7 @@ void free_matrix(sblas_ctx_s &C)
         if (d < (int)C.yptr.size()) (void)hipFree(C.yptr[d]);
     }
     C.yptr.clear();
+    C.vr.clear();
     C.A.clear();
     C.x.clear();
     C.ylocal.clear();
@@ -668,6 +677,7 @@ int sblas_ctx_matrix_upload_ex(sblas_ctx C, int m, int n, const long long *rowpt
     C->lrows.assign(g, 0);
     C->lnnz.assign(g, 0);
     C->yoff.assign(g, 0);
+    C->vr.assign(g, {});
     std::vector<long long> si(g), ei(g);
     std::vector<int> sr(g), er(g), sf(g);
     if (partition == 0) {
@@ -703,6 +713,7 @@ int sblas_ctx_matrix_upload_ex(sblas_ctx C, int m, int n, const long long *rowpt
             C->plo.resize((size_t)C->parts + 1);
             for (int p = 0; p <= C->parts; ++p) C->plo[p] = (long long)p * ncmax / C->parts;
             C->P.assign((size_t)g * C->parts, nullptr);
+            C->pcount.assign((size_t)g * C->parts, 0);
             C->palgo.assign(g, algo);
             SBLAS_TRY(ensure_overlap_streams(*C));
         }
@@ -722,6 +733,12 @@ int sblas_ctx_matrix_upload_ex(sblas_ctx C, int m, int n, const long long *rowpt
                                              lrp.data(), lcol.data(), lval.data()));
             C->lrows[d] = lm;
             C->lnnz[d] = lz;
+            cyclic_value_ranges(m, rowptr, g, C->chunk_rows, d, 0, C->stride / C->chunk_rows, C->vr[d]);
+            for (int p = 0; C->parts > 1 && p < C->parts; ++p) {
+                std::vector<ValRange> pr;
+                cyclic_value_ranges(m, rowptr, g, C->chunk_rows, d, C->plo[p], C->plo[p + 1], pr);
+                C->pcount[(size_t)d * C->parts + p] = value_ranges_count(pr);
+            }
             st = sblas_csr_upload_slice(&C->A[d], C->dev[d], n, lrp.data(), lcol.data(), lval.data(), 0,
                                         (int)lm, 0, lz, C->st[d]);
             if (st == SBLAS_OK) st = sblas_csr_analyse(C->A[d], algo, C->st[d]);
@@ -730,6 +747,7 @@ int sblas_ctx_matrix_upload_ex(sblas_ctx C, int m, int n, const long long *rowpt
             C->lrows[d] = std::max(0, er[d] - sr[d] + 1);
             C->lnnz[d] = C->lrows[d] > 0 ? ei[d] + 1 - si[d] : 0;
             if (exchange == SBLAS_CTX_ALLREDUCE) C->yoff[d] = sr[d];
+            C->vr[d].push_back({si[d], ei[d] + 1});
             st = sblas_csr_upload_slice(&C->A[d], C->dev[d], n, rowptr, col, val, sr[d], er[d] + 1,
                                         si[d], ei[d] + 1, C->st[d]);
             if (st == SBLAS_OK) st = sblas_csr_analyse(C->A[d], algo, C->st[d]);
@@ -794,6 +812,54 @@ int sblas_ctx_parts(sblas_ctx C, int *parts)
     if (!C || !parts) return SBLAS_ERR_INVALID;
     *parts = C->loaded ? C->parts : 0;
     return SBLAS_OK;
+}
+
+int sblas_ctx_matrix_set_values(sblas_ctx C, const double *val)
+{
+    if (!C || !C->loaded || (!val && C->nnz > 0)) return SBLAS_ERR_INVALID;
+    int st = SBLAS_OK;
+    for (int d = 0; d < C->g && st == SBLAS_OK; ++d) {
+        DeviceGuard gd(C->dev[d]);
+        const long long cnt = value_ranges_count(C->vr[d]);
+        if (cnt != C->A[d]->nnz) {
+            set_error("sblas_ctx_matrix_set_values: device %d holds %lld entries, its ranges %lld", d,
+                      C->A[d]->nnz, cnt);
+            return SBLAS_ERR_INVALID;
+        }
+        if (cnt == 0) continue;
+        // the device's share: pinned staging, one copy, then every handle of
+        // the device on its main stream (stream-ordered with its steps)
+        double *h = nullptr, *dv = nullptr;
+        hipError_t e = hipHostMalloc(&h, sizeof(double) * (size_t)cnt);
+        if (e == hipSuccess) e = hipMalloc(&dv, sizeof(double) * (size_t)cnt);
+        if (e == hipSuccess) {
+            stage_values(C->vr[d], val, h);
+            e = hipMemcpyAsync(dv, h, sizeof(double) * (size_t)cnt, hipMemcpyHostToDevice, C->st[d]);
+        }
+        if (e == hipSuccess) st = sblas_csr_set_values(C->A[d], dv, C->st[d]);
+        long long off = 0;
+        for (int p = 0; e == hipSuccess && st == SBLAS_OK && C->parts > 1 && p < C->parts; ++p) {
+            sblas_csr H = C->P[(size_t)d * C->parts + p];
+            const long long pc = C->pcount[(size_t)d * C->parts + p];
+            if (H && H->nnz != pc) {
+                set_error("sblas_ctx_matrix_set_values: part %d of device %d holds %lld entries, its ranges %lld",
+                          p, d, H->nnz, pc);
+                st = SBLAS_ERR_INVALID;
+            } else if (H) {
+                st = sblas_csr_set_values(H, dv + off, C->st[d]);
+            }
+            off += pc;
+        }
+        // the staging buffers are this call's: wait until they have been read
+        if (e == hipSuccess) e = hipStreamSynchronize(C->st[d]);
+        (void)hipFree(dv);
+        (void)hipHostFree(h);
+        if (e != hipSuccess) {
+            set_error("sblas_ctx_matrix_set_values: %s", hipGetErrorString(e));
+            st = SBLAS_ERR_HIP;
+        }
+    }
+    return st;
 }
 
 int sblas_ctx_matrix_upload(sblas_ctx C, int m, int n, const long long *rowptr, const int *col,

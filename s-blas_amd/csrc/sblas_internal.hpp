@@ -93,6 +93,10 @@ struct Csr5Plan {
                                    // continue one row (calibrated together), else 0
     bool ready = false;
     int form = 2;                  // tile form (spmv.hip c5_form_env; alternatives in experiment builds)
+    // value refresh (values.hip): a panel sub-plan's tval slots as indices into the handle's CSR values,
+    // -1 for padding; built by the first sblas_csr_set_values, null until then (the plain form has none)
+    int *vmap = nullptr;           // [ntiles*kC5Tile]
+    int psplit = 0;                // panel form: the panel count its column split was made with
     // XCD-affine form (spmv.hip "CSR5 over column panels"): one tile plan per
     // column panel of the panel plan, panel p's tiles dealt to the XCDs with
     // blockIdx % P == p, alpha-scaled partial y per panel, then a reduce.
@@ -151,6 +155,10 @@ struct PanelPlan {
     int nlong = 0;
     bool degenerate = false;    // <= 1 non-empty panel: plain row split
     bool ready = false;
+    int psplit = 0;             // the panel count the column split was made with (P counts the live ones)
+    long long vcap = 0;         // slots of col / val, padding included
+    int *vmap = nullptr;        // [vcap] value refresh (values.hip): val's slots as indices into the
+                                // handle's CSR values, -1 for padding; null until the first set_values
 };
 
 // SpMM plan: 16-row blocks whose column union is dense enough run on MFMA
@@ -237,6 +245,13 @@ struct XsPlan {
     long long d2h_bytes = 0;     // bytes the build copied device -> host
     long long xrec_bytes = 0;    // size of xrec
     bool ready = false;
+    // value refresh (values.hip).  The planner's ranges are kept on the host so
+    // that the first sblas_csr_set_values can derive the map with the layout
+    // builder that built the plan; the map itself exists only from then on.
+    std::vector<XsRange> h_ranges;
+    int rows_cap = 0, nrows_cap = 0;
+    int *vmap = nullptr;         // [nchunks*256] per chunk, in the chunk's own value order: the
+                                 // slot's index into the handle's CSR values, -1 for padding
 };
 
 struct RsPlan {
@@ -286,6 +301,11 @@ struct sblas_csr_s {
     double col_adjacency = -1;  // its locality probe
     double col_maxshare = -1;   // its largest eighth-of-the-columns share of the sampled entries
     double col_scattered = -1;  // share of sampled rows whose columns span > n/4
+    // sblas_csr_set_values' record (sblas_csr_values_info)
+    long long sv_calls = 0;
+    double sv_build_s = 0.0;    // wall seconds of the last map build
+    bool sv_rebuilt = false;    // the last call rebuilt a plan (no map could be held)
+    bool sv_dropped_mm = false; // the last call dropped an SpMM plan
 };
 
 namespace sblas {
@@ -316,6 +336,28 @@ int xs_layout_device(sblas_csr_s &A, const std::vector<XsRange> &ranges, int row
                      hipStream_t s, std::vector<long long> &blk, bool &on_device);
 int xs_layout_host(sblas_csr_s &A, const std::vector<XsRange> &ranges, int rows_cap, int nrows_cap,
                    std::vector<long long> &blk, std::unique_ptr<unsigned char[]> &hbuf);
+
+// Value refresh (sblas_csr_set_values, values.hip).  A.val already holds the
+// new values when the sv_refresh_* functions run; d_val is the caller's array.
+// Each refreshes its plan's value buffers through the plan's map (built on
+// first use, over the index payload `payload`: payload[i] = i + 1, zero
+// padded, as a double array shaped like A.val), or, when the map cannot be
+// held, frees the plan and rebuilds it in the same form (*rebuilt = true).
+int sv_refresh_panel(sblas_csr_s &A, const double *d_val, const double *payload, hipStream_t s, bool *rebuilt);
+int sv_refresh_csr5(sblas_csr_s &A, const double *d_val, const double *payload, hipStream_t s, bool *rebuilt);
+int sv_refresh_xsort(sblas_csr_s &A, const double *d_val, const double *payload, hipStream_t s, bool *rebuilt);
+// its building blocks (values.hip): a map allocation ("sv_map_nomem" fails
+// it), payload -> map, the pull gather dst[slot] = map[slot] >= 0 ?
+// src[map[slot]] : 0 over `nslots` (even) slots in runs of 2^seg_shift slots
+// `stride` doubles apart, and CSR5's tile transposition of the values alone
+int *sv_map_alloc(long long nslots);
+int sv_map_from_payload(const double *pv, long long nslots, int seg_shift, long long stride, int *map,
+                        hipStream_t s);
+int sv_gather(double *dst, const int *map, const double *src, long long nnz, long long nslots, int seg_shift,
+              long long stride, hipStream_t s);
+int sv_c5_tiles(double *tval, const double *val, long long nnz, long long ntiles, hipStream_t s);
+int sv_c5_tiles_map(int *map, const double *pv, long long nnz, long long ntiles, hipStream_t s);
+constexpr int kSvFlat = 62;  // seg_shift of a contiguous buffer (one run)
 
 int build_spmm_plan(sblas_csr_s &A, int ncols, hipStream_t s);  // C width of the first call
 void free_spmm_plan(sblas_csr_s &A);
@@ -359,6 +401,8 @@ bool peer_denied();  // the test hook's state
 // looks), "xs_hostplan" (xsort layout built on the host; read there too: the
 // fourth option of the plan build), "xs_devplan_nomem"
 // (its device build's scratch allocation fails: the host fallback),
+// "sv_map_nomem" (sblas_csr_set_values: no value map can be allocated, the
+// plans are rebuilt instead),
 // "csr5_hostplan" (CSR5 descriptors built on the host), "spmm_ctile",
 // "spmm_mfma_fill" (SpMM plan form), "rs_panel", "csr5_panel", "panels"
 // (XCD-panel forms).

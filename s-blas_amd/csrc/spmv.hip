@@ -1052,6 +1052,7 @@ static void free_csr5_arrays(Csr5Plan &P)
     (void)hipFree(P.empty_rows);
     (void)hipFree(P.carry);
     (void)hipFree(P.head_run);
+    (void)hipFree(P.vmap);
     for (Csr5Plan &Q : P.panels) free_csr5_arrays(Q);
     (void)hipFree(P.desc);
     (void)hipFree(P.ypart);
@@ -1068,6 +1069,7 @@ struct PanelCsr {
     double *val = nullptr;
     std::vector<int> hrp;         // host copy of rowptr
     std::vector<long long> base;  // panel p's first element in col / val
+    long long cap = 0;            // slots of col / val
 };
 
 static int split_panels(const sblas_csr_s &A, int P, hipStream_t s, PanelCsr &o);
@@ -1115,6 +1117,7 @@ static int build_csr5_panels(sblas_csr_s &A, int Preq, hipStream_t s)
     SBLAS_HIP(hipMalloc(&P.desc, sizeof(Csr5Desc) * PL));
     SBLAS_HIP(hipMemcpy(P.desc, hd.data(), sizeof(Csr5Desc) * PL, hipMemcpyHostToDevice));
     P.P = PL;
+    P.psplit = Preq;
     P.ready = true;
     return SBLAS_OK;
 }
@@ -1439,6 +1442,7 @@ static int split_panels(const sblas_csr_s &A, int P, hipStream_t s, PanelCsr &o)
     SBLAS_HIP(hipMalloc(&o.rowptr, sizeof(int) * P * (m + 1)));
     SBLAS_HIP(hipMemsetAsync(o.rowptr, 0, sizeof(int) * P * (m + 1), s));
     const long long cap = ((A.nnz + 3) & ~3LL) + 4 * P + 4;
+    o.cap = cap;
     SBLAS_HIP(hipMalloc(&o.col, sizeof(int) * cap));
     SBLAS_HIP(hipMalloc(&o.val, sizeof(double) * cap));
     SBLAS_HIP(hipMemsetAsync(o.col, 0, sizeof(int) * cap, s));
@@ -1512,12 +1516,19 @@ static int default_panels(const sblas_csr_s &A)
     return P;
 }
 
+static int build_panel_plan_p(sblas_csr_s &A, int P, hipStream_t s);
+
 int build_panel_plan(sblas_csr_s &A, hipStream_t s)
 {
     if (A.pn.ready) return SBLAS_OK;
+    return build_panel_plan_p(A, default_panels(A), s);
+}
+
+// the plan over a split into P column panels
+static int build_panel_plan_p(sblas_csr_s &A, int P, hipStream_t s)
+{
     DeviceGuard g(A.device);
     PanelPlan &Q = A.pn;
-    const int P = default_panels(A);
     const long long m = A.m;
     PanelCsr pc;
     {
@@ -1528,6 +1539,8 @@ int build_panel_plan(sblas_csr_s &A, hipStream_t s)
         }
     }
     Q.P = P;
+    Q.psplit = P;
+    Q.vcap = pc.cap;
     Q.W = pc.W;
     Q.rowptr = pc.rowptr;
     Q.col = pc.col;
@@ -1633,15 +1646,8 @@ int launch_spmv_panel(const sblas_csr_s &A, double alpha, const double *x, doubl
     return SBLAS_OK;
 }
 
-void free_plans(sblas_csr_s &A)
+static void free_panel_plan(sblas_csr_s &A)
 {
-    DeviceGuard g(A.device);
-    (void)hipFree(A.rs.blocks);
-    (void)hipFree(A.rs.long_rows);
-    (void)hipFree(A.rs.partial);
-    A.rs = RsPlan{};
-    free_csr5_arrays(A.c5);
-    A.c5 = Csr5Plan{};
     PanelPlan &Q = A.pn;
     (void)hipFree(Q.rowptr);
     (void)hipFree(Q.col);
@@ -1651,9 +1657,128 @@ void free_plans(sblas_csr_s &A)
     (void)hipFree(Q.ypart);
     (void)hipFree(Q.partial);
     (void)hipFree(Q.long_rows);
+    (void)hipFree(Q.vmap);
     A.pn = PanelPlan{};
+}
+
+void free_plans(sblas_csr_s &A)
+{
+    DeviceGuard g(A.device);
+    (void)hipFree(A.rs.blocks);
+    (void)hipFree(A.rs.long_rows);
+    (void)hipFree(A.rs.partial);
+    A.rs = RsPlan{};
+    free_csr5_arrays(A.c5);
+    A.c5 = Csr5Plan{};
+    free_panel_plan(A);
     free_xsort_plan(A);
     free_spmm_plan(A);
+}
+
+// ---------------------------------------------------------------------------
+// Value refresh of the panel plan and of CSR5 (sblas_csr_set_values; the
+// scheme is described at the top of values.hip)
+// ---------------------------------------------------------------------------
+// The column split run over the index payload instead of the values: o.val's
+// slots then name their sources.  Waits for the device (split_panels does).
+static int split_payload(sblas_csr_s &A, int P, const double *payload, hipStream_t s, PanelCsr &o)
+{
+    double *const keep = A.val;
+    A.val = const_cast<double *>(payload);
+    const int st = split_panels(A, P, s, o);
+    A.val = keep;
+    return st;
+}
+
+int sv_refresh_panel(sblas_csr_s &A, const double *d_val, const double *payload, hipStream_t s, bool *rebuilt)
+{
+    PanelPlan &Q = A.pn;
+    if (!Q.ready || Q.degenerate) return SBLAS_OK;  // degenerate: the row split on A.val
+    if (!Q.vmap) {
+        int *map = payload ? sv_map_alloc(Q.vcap) : nullptr;
+        if (!map) {  // no room for a map: the plan again, from the new values, over the same split
+            const int P = Q.psplit;
+            free_panel_plan(A);
+            *rebuilt = true;
+            return build_panel_plan_p(A, P, s);
+        }
+        PanelCsr pc;
+        int st = split_payload(A, Q.psplit, payload, s, pc);
+        if (st == SBLAS_OK && pc.cap != Q.vcap) {
+            set_error("set_values: the panel split's payload has another shape than the plan");
+            st = SBLAS_ERR_HIP;
+        }
+        if (st == SBLAS_OK) st = sv_map_from_payload(pc.val, Q.vcap, kSvFlat, 0, map, s);
+        if (st == SBLAS_OK && hipStreamSynchronize(s) != hipSuccess) st = SBLAS_ERR_HIP;
+        free_panel_csr(pc);
+        if (st != SBLAS_OK) {
+            (void)hipFree(map);
+            return st;
+        }
+        Q.vmap = map;
+    }
+    return sv_gather(Q.val, Q.vmap, d_val, A.nnz, Q.vcap, kSvFlat, 0, s);
+}
+
+int sv_refresh_csr5(sblas_csr_s &A, const double *d_val, const double *payload, hipStream_t s, bool *rebuilt)
+{
+    Csr5Plan &P = A.c5;
+    if (!P.ready) return SBLAS_OK;
+    // plain form (device- or host-built descriptors): the tile transposition again
+    if (P.P == 0) return sv_c5_tiles(P.tval, d_val, A.nnz, P.ntiles, s);
+    bool have = true;
+    for (const Csr5Plan &S : P.panels) have = have && (S.vmap || S.ntiles == 0);
+    if (!have) {
+        const int PL = P.P;
+        std::vector<int *> maps((size_t)PL, nullptr);
+        bool room = payload != nullptr;
+        for (int q = 0; room && q < PL; ++q) {
+            const Csr5Plan &S = P.panels[(size_t)q];
+            if (S.ntiles && !(maps[(size_t)q] = sv_map_alloc(S.ntiles * kC5Tile))) room = false;
+        }
+        if (!room) {  // the plan again, from the new values, in the same form
+            for (int *p : maps) (void)hipFree(p);
+            const int form = P.form, preq = P.psplit;
+            free_csr5_arrays(P);
+            A.c5 = Csr5Plan{};
+            A.c5.form = form;
+            *rebuilt = true;
+            return build_csr5_panels(A, preq, s);
+        }
+        // a sub-plan's tiles are the transposition of its panel's slice of the
+        // split: the split over the payload, then the transposition as a map
+        const long long m = A.m;
+        PanelCsr pc;
+        int st = split_payload(A, P.psplit, payload, s, pc);
+        std::vector<int> live;
+        for (int p = 0; st == SBLAS_OK && p < pc.P; ++p)
+            if (pc.hrp[(size_t)p * (m + 1) + m] > 0) live.push_back(p);
+        if (st == SBLAS_OK && (int)live.size() != PL) {
+            set_error("set_values: the CSR5 panel split has another shape than the plan");
+            st = SBLAS_ERR_HIP;
+        }
+        for (int q = 0; st == SBLAS_OK && q < PL; ++q) {
+            const int p = live[(size_t)q];
+            const long long nz = pc.hrp[(size_t)p * (m + 1) + m];
+            const Csr5Plan &S = P.panels[(size_t)q];
+            if ((nz + kC5Tile - 1) / kC5Tile != S.ntiles) {
+                set_error("set_values: the CSR5 panel split has another shape than the plan");
+                st = SBLAS_ERR_HIP;
+            } else {
+                st = sv_c5_tiles_map(maps[(size_t)q], pc.val + pc.base[(size_t)p], nz, S.ntiles, s);
+            }
+        }
+        if (st == SBLAS_OK && hipStreamSynchronize(s) != hipSuccess) st = SBLAS_ERR_HIP;
+        free_panel_csr(pc);
+        if (st != SBLAS_OK) {
+            for (int *p : maps) (void)hipFree(p);
+            return st;
+        }
+        for (int q = 0; q < PL; ++q) P.panels[(size_t)q].vmap = maps[(size_t)q];
+    }
+    for (Csr5Plan &S : P.panels)
+        SBLAS_TRY(sv_gather(S.tval, S.vmap, d_val, A.nnz, S.ntiles * kC5Tile, kSvFlat, 0, s));
+    return SBLAS_OK;
 }
 
 }  // namespace sblas

@@ -433,6 +433,7 @@ void free_xsort_plan(sblas_csr_s &A)
     (void)hipFree(P.qhead);
     (void)hipFree(P.partial);
     (void)hipFree(P.xrec);
+    (void)hipFree(P.vmap);
     A.xs = XsPlan{};
 }
 
@@ -544,6 +545,9 @@ int build_xsort_plan(sblas_csr_s &A, hipStream_t s)
     A.plan_bytes[SBLAS_SPMV_XSORT] = (long long)(sizeof(XsRange) * std::max<size_t>(H.wide.size(), 1)) +
                                      (long long)hb_n + (long long)sizeof(int) * 32 +
                                      (long long)sizeof(double) * std::max<long long>(pbase, 1) + P.xrec_bytes;
+    P.h_ranges = ranges;  // for the value map of sblas_csr_set_values (values.hip)
+    P.rows_cap = H.rows_cap;
+    P.nrows_cap = H.nrows_cap;
     P.nranges = (int)ranges.size();
     P.nwide = (int)H.wide.size();
     P.nchunks = nchunks;

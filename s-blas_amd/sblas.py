@@ -130,6 +130,9 @@ _sig("sblas_spmm_info", _i, _p, _p)
 _sig("sblas_csr_get_deterministic", _i, _p, _p)
 _sig("sblas_csr_xsort_export", _i, _p, _i, _p, _ll, _p)
 _sig("sblas_csr_xsort_build_info", _i, _p, _p)
+_sig("sblas_csr_set_values", _i, _p, _p, _p)
+_sig("sblas_csr_values_info", _i, _p, _p)
+_sig("sblas_ctx_matrix_set_values", _i, _p, _p)
 _sig("sblas_ctx_create", _i, _p, _i, _p)
 _sig("sblas_ctx_destroy", _i, _p)
 _sig("sblas_ctx_ngpu", _i, _p, _p)
@@ -669,7 +672,8 @@ class DeviceCSR:
     def xsort_export(self, what: int) -> np.ndarray:
         """One buffer of the analysed XSORT plan as bytes (sblas_csr_xsort_export):
         0 chunk storage, 1 item records, 2 wide-range records, 3 the 32
-        initial claim heads."""
+        initial claim heads, 4 the value map of set_values (int32 per value
+        slot; raises until a set_values call has built it)."""
         nb = C.c_longlong()
         check(lib.sblas_csr_xsort_export(self.h, what, None, 0, C.byref(nb)), "csr_xsort_export")
         buf = np.zeros(max(nb.value, 1), np.uint8)
@@ -707,6 +711,20 @@ class DeviceCSR:
 
     def algorithmic_bytes(self, beta_nonzero: bool) -> int:
         return int(lib.sblas_spmv_algorithmic_bytes(self.h, int(beta_nonzero)))
+
+    def set_values(self, val_ptr: int, stream=None) -> None:
+        """New values for the handle's entries (sblas_csr_set_values): val_ptr is
+        the address of nnz float64 on the device, in the order of the arrays
+        the handle was made from.  Pattern and analysed plans are kept; an
+        SpMM plan is dropped and rebuilt by the next spmm."""
+        check(lib.sblas_csr_set_values(self.h, val_ptr, stream), "csr_set_values")
+
+    def values_info(self) -> dict:
+        """What set_values has done so far (sblas_csr_values_info)."""
+        v = np.zeros(6, np.float64)
+        check(lib.sblas_csr_values_info(self.h, ptr(v)), "csr_values_info")
+        return {"calls": int(v[0]), "map_algos": int(v[1]), "map_bytes": int(v[2]), "map_build_s": float(v[3]),
+                "rebuilt": bool(v[4]), "dropped_spmm": bool(v[5])}
 
     def close(self) -> None:
         if self.h:
@@ -754,6 +772,12 @@ class DeviceCtx:
         check(lib.sblas_ctx_matrix_upload_parts(self.h, m, n, ptr(rp), ptr(ci), ptr(v), algo, parts),
               "ctx_matrix_upload_parts")
         self.m = m
+
+    def set_values(self, val) -> None:
+        """New values (host, the global CSR's order) for the loaded matrix
+        (sblas_ctx_matrix_set_values); partition, plans and exchange are kept."""
+        v = np.ascontiguousarray(val, np.float64)
+        check(lib.sblas_ctx_matrix_set_values(self.h, ptr(v)), "ctx_matrix_set_values")
 
     def parts(self) -> int:
         p = C.c_int()
