@@ -230,6 +230,44 @@ int sblas_csr_get_deterministic(sblas_csr A, int *on);
  * entries, i.e. P = 8 on config 2.  PANEL always does (unless only one panel
  * holds entries). */
 int sblas_csr_panels(sblas_csr A, int algo, int *panels);
+/* What the row-split, CSR5 and XCD-panel SpMV decide on the host before a plan
+ * is built, for any matrix and without a GPU (pure functions of their
+ * arguments: they read neither the environment nor the test hooks).
+ * sblas_spmv_shape_host: algo 0..5 (sblas_spmv_algo); adjacency, share
+ * (largest eighth of the columns) and scattered are the column probe's
+ * results; auto_env is SBLAS_AUTO's value (0 or out of 1..5: ignored);
+ * rs_panel / csr5_panel (1 / 0 forces the form), panels (the count, 1..64)
+ * and csr5_hostplan are the test hooks of the same names, -1 = unset.
+ * info[6] = the algorithm that runs (AUTO resolved), whether its plan runs
+ * over XCD column panels, the panel count its column split is made with (0 for
+ * XSORT), the panel width in columns, CSR5's descriptors built on the host,
+ * and whether the plan build runs the column probe for this request at all.
+ * sblas_rowsplit_blocks_host: the row blocks of a host rowptr (rowptr[0] = 0).
+ * info[6] = blocks, stream blocks, single-chunk long rows (2049..8192
+ * entries), multi-chunk long rows, partial slots, the most rows in one block;
+ * blocks (NULL: sizes only) receives {row, a, b} per block: a stream block
+ * of rows [row, a), or chunk -a-1 of long row `row` with partial slot b (-1:
+ * the chunk writes y).
+ * sblas_csr5_plan_host: CSR5's tile descriptors.  info[6] = tiles, tiles
+ * with empty rows (bit 31 of tile_row), seg_row entries, empty rows, head
+ * runs, the longest head run (tiles).  Each array may be NULL: flags
+ * [64*tiles], tile_row and seg_off [tiles+1], seg_row [info[2]], empty_rows
+ * [info[3]], head_run [tiles].
+ * sblas_csr_spmv_info: the same counts from a handle's analysed plan.  ROWSPLIT
+ * and PANEL: info[8] = live panels the blocks run over (0: the plain row
+ * split), the six counts of sblas_rowsplit_blocks_host summed over those
+ * panels, the panel count of the split.  CSR5: live panels (0: plain),
+ * tiles, tiles with empty rows, seg_row entries, empty rows (each summed over
+ * the panels), the panel count of the split, 0, 0.  SBLAS_ERR_INVALID before
+ * the analysis, and for AUTO and XSORT. */
+int sblas_spmv_shape_host(int algo, int m, int n, long long nnz, double adjacency, double share,
+                          double scattered, int auto_env, int rs_panel, int csr5_panel, int panels,
+                          int csr5_hostplan, long long *info);
+int sblas_rowsplit_blocks_host(int m, const long long *rowptr, long long *info, int *blocks,
+                               long long blocks_cap);
+int sblas_csr5_plan_host(int m, const long long *rowptr, long long *info, unsigned *flags, int *tile_row,
+                         int *seg_off, int *seg_row, int *empty_rows, int *head_run);
+int sblas_csr_spmv_info(sblas_csr A, int algo, long long *info);
 /* Device bytes held by the analysis of `algo` (free memory before - after
  * sblas_csr_analyse; XSORT: the sum of its plan's allocations, the same for
  * the device and the host build; 0 if not analysed): the layout's cost

@@ -297,8 +297,6 @@ __global__ __launch_bounds__(256) void k_col_adjacency(const int *__restrict__ r
     }
 }
 
-constexpr long long kAutoXsortMinNnz = 2000000;  // bench slices: xsort leads from ~2M nnz
-
 }  // namespace
 
 extern "C++" {
@@ -352,27 +350,10 @@ namespace {
 int pick_algo(sblas_csr_s &A, hipStream_t s)
 {
     if (A.auto_algo) return A.auto_algo;
-    if (const int st = probe_columns(A, s)) return -st;
-    const double adj = A.col_adjacency, share = A.col_maxshare;
-    // The column-sorted kernel wherever it applies at size and its column
-    // groups share the work: it leads on random columns (config 2: 0.51 of
-    // 8 TB/s vs 0.21 row split) and on banded / stencil matrices too (3-D
-    // 27-point stencil 0.84 vs 0.55, 7-point 0.71 vs 0.58), but
-    // columns crowded into one eighth (the reference generator's prefix
-    // columns) leave one XCD all of it: the row split there (0.68), as for
-    // any matrix whose rows read neighbouring x lines; the XCD-panel row
-    // split below 2M nonzeros.
-    const bool spread = share <= 0.25;  // no eighth of the columns holds > 2x its share
-    int algo;
-    if (A.nnz >= kAutoXsortMinNnz && (long long)A.n * 8 <= (120LL << 20) && spread) algo = SBLAS_SPMV_XSORT;
-    else if (adj >= 0.5 || !spread) algo = SBLAS_SPMV_ROWSPLIT;
-    else algo = SBLAS_SPMV_PANEL;
-    if (const char *o = getenv("SBLAS_AUTO")) {
-        const int v = atoi(o);
-        if (v >= SBLAS_SPMV_ROWSPLIT && v <= SBLAS_SPMV_XSORT) algo = v;
-    }
-    A.auto_algo = algo;
-    return algo;
+    SpmvShape S;  // the probe, then the rule (spmv_shape.cpp)
+    if (const int st = spmv_plan_shape(A, SBLAS_SPMV_AUTO, s, &S)) return -st;
+    A.auto_algo = S.algo;
+    return S.algo;
 }
 
 // algo, or AUTO resolved (negative: -status)
@@ -525,6 +506,33 @@ int sblas_csr_panels(sblas_csr A, int algo, int *panels)
     case SBLAS_SPMV_PANEL: *panels = A->pn.ready && !A->pn.degenerate ? A->pn.P : 0; break;
     default: *panels = 0; break;
     }
+    return SBLAS_OK;
+}
+
+int sblas_csr_spmv_info(sblas_csr A, int algo, long long *info)
+{
+    if (!A || !info || !plan_ready(*A, algo) || algo == SBLAS_SPMV_XSORT) return SBLAS_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    if (algo == SBLAS_SPMV_CSR5 || algo == SBLAS_SPMV_CSR5_ALT) {
+        const Csr5Plan &P = A->c5;
+        info[0] = P.P;
+        info[5] = P.psplit;
+        const Csr5Plan *sub = P.P ? P.panels.data() : &P;
+        for (int q = 0; q < std::max(P.P, 1); ++q) {
+            info[1] += sub[q].ntiles;
+            info[2] += sub[q].ngap;
+            info[3] += sub[q].nsegrow;
+            info[4] += sub[q].nempty;
+        }
+        return SBLAS_OK;
+    }
+    // the row blocks that run: the panel plan's, or the plain row split's
+    // (which also serves a panel plan with fewer than two non-empty panels)
+    const bool panels = algo == SBLAS_SPMV_ROWSPLIT ? A->rs.panels : !A->pn.degenerate;
+    const long long *c = panels ? A->pn.counts : A->rs.counts;
+    info[0] = panels ? A->pn.P : 0;
+    for (int i = 0; i < kRowBlockCounts; ++i) info[1 + i] = c[i];
+    info[7] = panels ? A->pn.psplit : 0;
     return SBLAS_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/sblas.h"
+#include "spmv_shape.hpp"
 #include "xsort.hpp"
 
 namespace sblas {
@@ -55,28 +56,8 @@ LaunchTimer &launch_timer();
         if (s_ != SBLAS_OK) return s_;                                         \
     } while (0)
 
-// Row-split (CSR-adaptive) tuning. One 256-thread workgroup per row block.
-constexpr int kRsThreads = 256;
-#ifndef SBLAS_RS_BLOCK_NNZ  // experiment builds only (Makefile `alt`)
-#define SBLAS_RS_BLOCK_NNZ 2048
-#endif
-constexpr int kRsBlockNnz = SBLAS_RS_BLOCK_NNZ;  // LDS product stream capacity (16 KiB f64)
-constexpr int kRsMaxRows = 1024;    // rows per stream block
-constexpr int kRsLongChunk = 8192;  // nnz per workgroup for long rows
-
-// Row block descriptor (16 B): stream block when a > row (a = end row);
-// long-row chunk when a < 0 (chunk k = -a-1, b = partial slot or -1).
-struct RowBlock {
-    int row;
-    int a;
-    int b;
-    int c;
-};
-
-// CSR5-style tiles: 64 lanes x kC5Sigma nnz per tile (one wave per tile).
-constexpr int kC5Lanes = 64;
-constexpr int kC5Sigma = 16;
-constexpr int kC5Tile = kC5Lanes * kC5Sigma;
+// The row split's tuning constants and RowBlock, CSR5's tile constants:
+// spmv_shape.hpp (shared with the host-only planner).
 
 struct Csr5Plan {
     long long ntiles = 0;
@@ -92,7 +73,8 @@ struct Csr5Plan {
     int *head_run = nullptr;       // [ntiles] > 0: tile t starts a run of that many tiles whose heads
                                    // continue one row (calibrated together), else 0
     bool ready = false;
-    int form = 2;                  // tile form (spmv.hip c5_form_env; alternatives in experiment builds)
+    int nsegrow = 0;               // entries of seg_row
+    long long ngap = 0;            // tiles with bit31 set (csr5_gap_tiles; sblas_csr_spmv_info)
     // value refresh (values.hip): a panel sub-plan's tval slots as indices into the handle's CSR values,
     // -1 for padding; built by the first sblas_csr_set_values, null until then (the plain form has none)
     int *vmap = nullptr;           // [ntiles*kC5Tile]
@@ -159,6 +141,7 @@ struct PanelPlan {
     long long vcap = 0;         // slots of col / val, padding included
     int *vmap = nullptr;        // [vcap] value refresh (values.hip): val's slots as indices into the
                                 // handle's CSR values, -1 for padding; null until the first set_values
+    long long counts[kRowBlockCounts] = {0, 0, 0, 0, 0, 0};  // count_row_blocks over the live panels
 };
 
 // SpMM plan: 16-row blocks whose column union is dense enough run on MFMA
@@ -262,8 +245,8 @@ struct RsPlan {
     double *partial = nullptr;     // [nslots]
     int nslots = 0;
     bool ready = false;
-    bool panels = false;           // run as the panel plan (XCD column panels, spmv.hip xcd_panels_pay)
-    bool seq = true;               // consecutive entries per thread (experiment build SBLAS_RS_SEQ=0: vec4 order)
+    bool panels = false;           // run as the panel plan (XCD column panels, spmv_shape.cpp)
+    long long counts[kRowBlockCounts] = {0, 0, 0, 0, 0, 0};  // count_row_blocks
 };
 
 }  // namespace sblas
@@ -366,8 +349,8 @@ int launch_spmm(const sblas_csr_s &A, int n, double alpha, const double *B,
                 hipStream_t s);
 int launch_transpose(const sblas_csr_s &A, int *colptr, int *rowidx,
                      double *cval, hipStream_t s, int *colidx = nullptr);
-void make_row_blocks(const int *rp, int m, std::vector<RowBlock> &blocks,
-                     std::vector<int4> &longs, int &nslots);
+// the host shape of a plan build (spmv.hip: hooks, the probe on demand, spmv_shape)
+int spmv_plan_shape(sblas_csr_s &A, int algo, hipStream_t s, SpmvShape *S);
 int launch_rowsplit_raw(const int *rowptr, const int *col, const double *val, const double *x,
                         const RowBlock *blocks, int nblocks, const int4 *long_rows, int nlong,
                         double *partial, double alpha, double beta, double *y, hipStream_t s);

@@ -217,7 +217,7 @@ extern "C" int sblas_spmv_ooc(int m, int n, long long nnz, double alpha, const l
             }
             setup_ns += (long long)((sblas_get_time() - ts) * 1e9);
             std::vector<RowBlock> blocks;
-            std::vector<int4> longs;
+            std::vector<LongRow> longs;
             int k = 0;
             while (ok && status.load() == SBLAS_OK) {
                 const int t = next.fetch_add(1);

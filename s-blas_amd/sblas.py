@@ -146,6 +146,10 @@ _sig("sblas_ctx_slice_algo", _i, _p, _i, _p)
 _sig("sblas_ctx_matrix_upload_parts", _i, _p, _i, _i, _p, _p, _p, _i, _i)
 _sig("sblas_ctx_parts", _i, _p, _p)
 _sig("sblas_csr_panels", _i, _p, _i, _p)
+_sig("sblas_spmv_shape_host", _i, _i, _i, _i, _ll, _d, _d, _d, _i, _i, _i, _i, _i, _p)
+_sig("sblas_rowsplit_blocks_host", _i, _i, _p, _p, _p, _ll)
+_sig("sblas_csr5_plan_host", _i, _i, _p, _p, _p, _p, _p, _p, _p, _p)
+_sig("sblas_csr_spmv_info", _i, _p, _i, _p)
 _sig("sblas_ctx_spmv_ex", _i, _p, _d, _d, _d, _i, _p)
 _sig("sblas_ctx_sync", _i, _p, _p)
 _sig("sblas_ctx_get_y", _i, _p, _i, _p)
@@ -265,6 +269,51 @@ def xsort_plan_host(rowptr, n: int, resident: int, cap=None, allwide=None, solo=
     out = {k: int(v) for k, v in zip(keys, info)}
     out["qlen"], out["qstat"], out["ranges"] = info[11:19].copy(), info[19:27].copy(), ranges
     out["queues"] = np.split(items, np.cumsum(out["qlen"])[:-1])
+    return out
+
+
+ROWSPLIT_BLOCK_KEYS = ("blocks", "stream", "long1", "longn", "slots", "max_rows")
+
+
+def spmv_shape_host(algo: int, m: int, n: int, nnz: int, adjacency: float = 0.0, share: float = 1.0,
+                    scattered: float = 0.0, auto_env: int = 0, rs_panel: int = -1, csr5_panel: int = -1,
+                    panels: int = -1, csr5_hostplan: int = -1) -> dict:
+    """What the SpMV plan build decides before it builds (sblas_spmv_shape_host;
+    no GPU, reads neither the environment nor the test options: pass them in,
+    -1 = unset): algo (AUTO resolved), panels (runs over XCD column panels),
+    npanels (the split's count), W (columns per panel), c5_host, wants_probe.
+    rowsplit_blocks_host / csr5_plan_host: the row blocks and CSR5's tile
+    descriptors of a rowptr, counts first (see sblas.h)."""
+    info = np.zeros(6, np.int64)
+    check(lib.sblas_spmv_shape_host(algo, m, n, nnz, adjacency, share, scattered, auto_env, rs_panel, csr5_panel,
+                                    panels, csr5_hostplan, ptr(info)), "spmv_shape_host")
+    return {k: int(v) for k, v in zip(("algo", "panels", "npanels", "W", "c5_host", "wants_probe"), info)}
+
+
+def rowsplit_blocks_host(rowptr) -> dict:
+    rp = np.ascontiguousarray(rowptr, np.int64)
+    info = np.zeros(6, np.int64)
+    check(lib.sblas_rowsplit_blocks_host(len(rp) - 1, ptr(rp), ptr(info), None, 0), "rowsplit_blocks_host")
+    blocks = np.zeros((int(info[0]), 3), np.int32)
+    check(lib.sblas_rowsplit_blocks_host(len(rp) - 1, ptr(rp), ptr(info), ptr(blocks), len(blocks)),
+          "rowsplit_blocks_host")
+    out = {k: int(v) for k, v in zip(ROWSPLIT_BLOCK_KEYS, info)}
+    out["list"] = blocks
+    return out
+
+
+def csr5_plan_host(rowptr) -> dict:
+    rp = np.ascontiguousarray(rowptr, np.int64)
+    m = len(rp) - 1
+    info = np.zeros(6, np.int64)
+    check(lib.sblas_csr5_plan_host(m, ptr(rp), ptr(info), None, None, None, None, None, None), "csr5_plan_host")
+    nt = int(info[0])
+    a = dict(flags=np.zeros(64 * nt, np.uint32), tile_row=np.zeros(nt + 1, np.int32),
+             seg_off=np.zeros(nt + 1, np.int32), seg_row=np.zeros(int(info[2]), np.int32),
+             empty_rows=np.zeros(int(info[3]), np.int32), head_run=np.zeros(nt, np.int32))
+    check(lib.sblas_csr5_plan_host(m, ptr(rp), ptr(info), *(ptr(v) for v in a.values())), "csr5_plan_host")
+    out = {k: int(v) for k, v in zip(("tiles", "gap_tiles", "seg_rows", "n_empty", "head_runs", "longest_run"), info)}
+    out.update(a)
     return out
 
 
@@ -704,6 +753,16 @@ class DeviceCSR:
         p = C.c_int()
         check(lib.sblas_csr_panels(self.h, algo, C.byref(p)), "csr_panels")
         return p.value
+
+    def spmv_info(self, algo: int) -> dict:
+        """What the analysed plan of `algo` runs (sblas_csr_spmv_info): ROWSPLIT and
+        PANEL give panels + ROWSPLIT_BLOCK_KEYS + psplit, CSR5 panels, tiles,
+        gap_tiles, seg_rows, empty_rows, psplit; sums over the live panels."""
+        info = np.zeros(8, np.int64)
+        check(lib.sblas_csr_spmv_info(self.h, algo, ptr(info)), "csr_spmv_info")
+        keys = (("panels", "tiles", "gap_tiles", "seg_rows", "empty_rows", "psplit") if algo in (CSR5, 3)
+                else ("panels",) + ROWSPLIT_BLOCK_KEYS + ("psplit",))
+        return {k: int(v) for k, v in zip(keys, info)}
 
     def plan_bytes(self, algo: int) -> int:
         """Device bytes the algorithm's analysis holds beside the CSR."""

@@ -24,6 +24,8 @@ def exported(demangle):
 def test_c_abi_symbols(sb):
     names = declared("sblas.h", r"\b(sblas_\w+)\s*\(")
     assert len(names) >= 30
+    assert {"sblas_spmv_shape_host", "sblas_rowsplit_blocks_host", "sblas_csr5_plan_host",
+            "sblas_csr_spmv_info"} <= set(names)
     syms = exported(False)
     missing = [n for n in names if n not in syms]
     assert not missing, missing

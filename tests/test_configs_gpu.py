@@ -158,7 +158,7 @@ def test_config2_xcd_panel_choice(torch_cuda, sb, cfg2):
     columns (x = 16 MB > 8 MiB, 39.75M nnz, rows spanning most of x): 4 for
     the row split, 8 for CSR5 from 32M entries; both keep the plain layout on
     the reference generator's prefix columns; PANEL always uses panels
-    (sblas_csr_panels, spmv.hip xcd_panels_pay)."""
+    (sblas_csr_panels, the rule in spmv_shape.cpp)."""
     A = sb.DeviceCSR.upload(0, N2, cfg2["rp"], cfg2["col"], cfg2["val"])
     try:
         for algo in (sb.ROWSPLIT, sb.CSR5, sb.PANEL):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from spmv_cases import empty_runs, ragged, random_csr, tile_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -49,20 +50,6 @@ def algo(request, sb):
     with sb.test_options(**opts):
         yield a
     DET["on"] = False
-
-
-def random_csr(rng, m, n, density_rows, long_rows=(), empty_frac=0.1):
-    lens = rng.integers(0, density_rows, size=m)
-    lens[rng.random(m) < empty_frac] = 0
-    for r, L in long_rows:
-        lens[r] = L
-    lens = np.minimum(lens, n)
-    rp = np.zeros(m + 1, np.int64)
-    rp[1:] = np.cumsum(lens)
-    col = np.concatenate([np.sort(rng.choice(n, size=L, replace=False)) for L in lens]
-                         ).astype(np.int32) if rp[-1] else np.zeros(0, np.int32)
-    val = rng.standard_normal(int(rp[-1]))
-    return rp, col, val
 
 
 def run_gpu(torch, sb, algo, n, rp, col, val, x, alpha, beta, y0, det=None):
@@ -171,24 +158,8 @@ def test_csr5_device_plan_matches_host_plan(torch_cuda, sb, orc, monkeypatch, ca
     empty-row segment lists; format_cuda.h:21-300's job) give the same y, bit
     for bit, as the host-built descriptors (test option csr5_hostplan)."""
     rng = np.random.default_rng(11)
-    if case == "ragged":
-        m, n = 3000, 40000
-        rp, col, val = random_csr(rng, m, n, 60, long_rows=[(5, 2049), (17, 8192), (900, 30000)])
-    elif case == "empty_runs":  # long runs of empty rows inside and across tiles
-        m, n = 20000, 5000
-        lens = np.zeros(m, np.int64)
-        live = rng.choice(m, 900, replace=False)
-        lens[live] = rng.integers(1, 40, 900)
-        lens[-1] = 3000
-        rp = np.concatenate([[0], np.cumsum(lens)])
-        col = np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens]).astype(np.int32)
-        val = rng.standard_normal(int(rp[-1]))
-    elif case == "tile_rows":  # rows of exactly one tile, and of 1 / 16 entries
-        m, n = 600, 3000
-        lens = rng.choice([1, 16, 1024, 0], m)
-        rp = np.concatenate([[0], np.cumsum(lens)])
-        col = np.concatenate([np.sort(rng.choice(n, L, replace=False)) for L in lens]).astype(np.int32)
-        val = rng.standard_normal(int(rp[-1]))
+    if case != "synth":  # the generators of spmv_cases.py (their descriptors: test_spmv_shape_cpu.py)
+        m, n, rp, col, val = {"ragged": ragged, "empty_runs": empty_runs, "tile_rows": tile_rows}[case](rng)
     else:
         m = n = 20000
         rp, col, val = orc.gen_synth(n)
